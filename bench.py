@@ -1,8 +1,15 @@
 #!/usr/bin/env python3
 """bench.py - RJMCMC birth-death likelihood loop on MI355X: lineage-log-lik evals/s.
 
-    python bench.py [--gpus N --steps K --warmup W]          (N > 1 without WORLD_SIZE: starts its own N ranks)
+    python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]   (N > 1 without WORLD_SIZE: starts its own N ranks)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the line: the headline, the config, and the roofline as far
+as the timed region's own HIP events give it (the persistent engines).  Whatever takes runs of its own - the launch-based
+engine's scan timing, the copy yardstick and rocprofv3 traffic of the roofline, and the sections below - is measured
+under --full only (each part still switched off by its --no-* option).  --dump-outputs DIR writes the chain states the
+last timed step left, and the last trace row sampled in the timed region, as DIR/<name>.npy (float64, finite; inputs and
+seeds are fixed, so two builds can be compared output for output).
 
 A "step" = one RJMCMC iteration of every chain on this GPU: one scan of the lineages scoring all pending proposals
 + the per-chain accept / trace / next-proposal step, all inside the persistent engine kernel (one launch runs the K
@@ -18,6 +25,7 @@ Beside the headline the line carries
   roofline      - the dominant kernel against its physical bound (the LDS gather rate), with the
                   HBM figures SURVEY 8(d) asks for as side fields and the HBM traffic measured by a rocprofv3 --pmc
                   child run of the same launch (null + the reason when the profiler is not usable);
+under --full:
   configs       - the other BASELINE configurations (cfg2, cfg3, cfg5), cfg4 on general (non-integer) lineage times,
                   and cfg4 exactly as BASELINE.json words it (1024 chains over 8 GPUs = a 128-chain shard);
   strong_scaling- for N > 1: the same 1024 chains in total, sharded over the N ranks, timed the same way;
@@ -796,7 +804,7 @@ def compact_line(d):
     """The final stdout line: every field the driver's contract names + `roofline` + `cpu_baseline` + one-number
     summaries of the side sections - scalars and short names only, no prose; everything else stays in the detail
     (bench_detail.json, and `#detail` lines on stderr).  Pure function of the detail dict."""
-    cfg, r, c = d["config"], d["roofline"], d.get("cpu_baseline")
+    cfg, r, c = d["config"], d["roofline"] or {}, d.get("cpu_baseline")
     out = {k: (_sig(d[k], 9) if isinstance(d[k], float) else d[k]) for k in (
         "metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
         "dtype", "data")}
@@ -886,6 +894,45 @@ def emit(detail, stream=None, detail_stream=None):
     return line
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(snap, trace_last, path):
+    """--dump-outputs: what the engine hands its caller after the last timed step, as float64 `path/<name>.npy`, finite
+    values only.  Every chain's accepted state (engine.snapshot()): the scalars one per chain, the ragged rate and
+    shift-time lists concatenated chain after chain (`L`, `tL` hold K_l and K_l + 1 values per chain, `M`, `tM` K_m and
+    K_m + 1).  The last trace row sampled inside the timed region (None when the region sampled none) as split_trace_row
+    gives it: the 13 log columns per chain (`trace_head`) and the sampled rates with their interior shift times,
+    concatenated the same way (`trace_sp`, `trace_ex`).  When the chains could exceed DUMP_LIMIT_BYTES, a fixed seeded
+    sample of them is written (the sample depends on the chain count alone), with its indices in `chain_index.npy`."""
+    from literate_amd import _hip
+    from literate_amd.engine import split_trace_row
+    K = _hip.LR_KMAX
+    n = len(snap["L"])
+    per_chain = 8 * ((4 * K + 2) + 9 + _hip.LR_TRACE_HEAD + 2 * (2 * K - 1))      # bytes a chain can take at most
+    idx = np.arange(n)
+    if n * per_chain > DUMP_LIMIT_BYTES:
+        idx = np.sort(np.random.default_rng(0).choice(n, max(1, DUMP_LIMIT_BYTES // per_chain - 1), replace=False))
+
+    def flat(rows):
+        return np.concatenate([np.asarray(rows[c], dtype=np.float64) for c in idx])
+
+    arrays = {k: flat(snap[k]) for k in ("L", "M", "tL", "tM")}
+    for k in ("likA", "priorA", "gamma_rate", "poi", "K_l", "K_m", "accepted", "it"):
+        arrays[k] = np.asarray(snap[k], dtype=np.float64)[idx]
+    if trace_last is not None:
+        rows = [split_trace_row(np.asarray(trace_last[c], dtype=np.float64)) for c in idx]
+        arrays["trace_head"] = np.stack([r[0] for r in rows])
+        arrays["trace_sp"] = np.concatenate([r[1] for r in rows])
+        arrays["trace_ex"] = np.concatenate([r[2] for r in rows])
+    if len(idx) < n:
+        arrays["chain_index"] = idx.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(a))
+    return sorted(arrays)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -897,6 +944,11 @@ def main():
                     help="weak: the workload's chains on EVERY GPU; strong: that many chains in total, sharded over the ranks")
     ap.add_argument("--engine", default="auto", choices=("auto", "launch", "persistent", "persistent4"))
     ap.add_argument("--sample-every", type=int, default=100, help="trace sampling frequency (-s)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: scan timing and copy yardstick of the roofline, rocprofv3 "
+                         "traffic, the other configurations, strong scaling (N > 1), the CPU baseline and the `abi` section")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the chain states after the last timed step (and the region's last trace row) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-configs", action="store_true", help="skip the side configurations (cfg2, cfg3, cfg5, ...)")
     ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 --pmc child runs (roofline.traffic = null)")
@@ -975,7 +1027,7 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    def timed_region(scaling):
+    def timed_region(scaling, dump_dir=None):
         """W warm-up + exactly K timed iterations of this rank's shard; returns the figures of the region."""
         if scaling == "weak":
             offset, chains = rank * base_chains, base_chains
@@ -1035,9 +1087,11 @@ def main():
         snap = eng.snapshot()
         assert np.all(snap["it"] == args.steps + args.warmup) and np.all(np.isfinite(snap["likA"]))
         assert snap["accepted"].min() > 0
+        if dump_dir and rank == 0:
+            dump_outputs(snap, eng.trace[s1 - 1].cpu().numpy() if s1 > s0 else None, dump_dir)
         return eng, chains, total, elapsed, region_kernel_ms, rows
 
-    eng, chains, total_chains, elapsed, region_kernel_ms, rows_gathered = timed_region(args.scaling)
+    eng, chains, total_chains, elapsed, region_kernel_ms, rows_gathered = timed_region(args.scaling, args.dump_outputs)
     value = args.steps * n_lin * total_chains / elapsed
 
     out = None
@@ -1046,6 +1100,7 @@ def main():
         unit = bool(eng.unit_resolution)
         cb = eng.layout.chains_per_block
         kname = eng.kernel_name()
+        roof = None
         if persistent:
             # Dominant kernel = the persistent engine kernel: ONE launch runs n_ev iterations of every chain.  Timed
             # live with HIP events recorded on its stream around the launches of the timed region itself
@@ -1055,7 +1110,7 @@ def main():
             kernel_ms = region_kernel_ms / launches
             cb_pass = chains_per_gather(eng)                        # chains one pass over the packed lineages scores
             passes = n_ev * (-(-chains // cb_pass))                 # lineage passes per launch
-        else:
+        elif args.full:
             # launch-based engine: the lineage scan runs as the scan blocks of lr_fused_iter_kernel, which HIP
             # events cannot bracket launch by launch under graph replay; the SAME block body is timed live as the
             # stand-alone lr_scan_*_kernel over all chains (lr_mcmc_time_scan, back-to-back launches)
@@ -1065,25 +1120,29 @@ def main():
                 cb, eng.layout.table_stride // (1 if unit else 2))
             passes = -(-chains // cb)
             cb_pass = cb
-        fig = kernel_figures(eng, n_lin, chains, n_ev, kernel_ms)
-        roof = roofline_object(fig, kname, kernel_ms, n_ev, n_lin, chains, passes, cb_pass)
-        roof["frac_engine"] = value / world * fig["lds_bytes_per_eval"] / 1e9 / LDS_PEAK_GBS
-        # yardstick beside the nominal 8 TB/s: device-to-device copy of 1 GiB, read + write bytes
-        src = torch.empty(1 << 30, dtype=torch.uint8, device="cuda")
-        dst = torch.empty_like(src)
-        dst.copy_(src)
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
-        for _ in range(10):
+        fig = eval_cost(eng)
+        if persistent or args.full:
+            fig = kernel_figures(eng, n_lin, chains, n_ev, kernel_ms)
+            roof = roofline_object(fig, kname, kernel_ms, n_ev, n_lin, chains, passes, cb_pass)
+            roof["frac_engine"] = value / world * fig["lds_bytes_per_eval"] / 1e9 / LDS_PEAK_GBS
+        if args.full:
+            # yardstick beside the nominal 8 TB/s: device-to-device copy of 1 GiB, read + write bytes
+            src = torch.empty(1 << 30, dtype=torch.uint8, device="cuda")
+            dst = torch.empty_like(src)
             dst.copy_(src)
-        ev1.record()
-        torch.cuda.synchronize()
-        roof["hbm"]["copy_GBs_measured"] = 10 * 2.0 * src.numel() / (ev0.elapsed_time(ev1) * 1e-3) / 1e9
-        del src, dst
-        roof["engine"] = {"persistent": fig["persistent"], "threads_per_block": fig["threads_per_block"],
-                          "chains_per_block": {1: 2, 2: 4, 3: chains_per_gather(eng)}[int(eng.layout.persistent)] if persistent else cb,
-                          "team_blocks": int(eng.layout.team_blocks), "table_mode": int(eng.layout.table_mode),
-                          "unit_resolution_tables": unit, "us_per_iter_device": fig["us_per_iter"]}
+            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            ev0.record()
+            for _ in range(10):
+                dst.copy_(src)
+            ev1.record()
+            torch.cuda.synchronize()
+            roof["hbm"]["copy_GBs_measured"] = 10 * 2.0 * src.numel() / (ev0.elapsed_time(ev1) * 1e-3) / 1e9
+            del src, dst
+        if roof is not None:
+            roof["engine"] = {"persistent": fig["persistent"], "threads_per_block": fig["threads_per_block"],
+                              "chains_per_block": {1: 2, 2: 4, 3: chains_per_gather(eng)}[int(eng.layout.persistent)] if persistent else cb,
+                              "team_blocks": int(eng.layout.team_blocks), "table_mode": int(eng.layout.table_mode),
+                              "unit_resolution_tables": unit, "us_per_iter_device": fig["us_per_iter"]}
         out = {
             "metric": "RJMCMC iters/sec x lineages (lineage-log-lik evals/s, summed over chains)",
             "value": value, "unit": "lineage-log-lik evals/s", "n_gpus": world, "steps": args.steps,
@@ -1117,7 +1176,7 @@ def main():
     del eng
 
     # ---- N > 1: the configuration as BASELINE.json words it (the chains in total, sharded) -----------------------
-    if world > 1 and args.scaling == "weak":
+    if world > 1 and args.scaling == "weak" and args.full:
         eng2, chains2, total2, elapsed2, kms2, rows2 = timed_region("strong")
         if rank == 0:
             out["strong_scaling"] = {"chains_total": total2, "chains_per_gpu": chains2,
@@ -1127,7 +1186,7 @@ def main():
         eng2.close()
         del eng2
 
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and args.full:
         r = out["roofline"]
         if not args.no_pmc:
             traffic, note = measure_traffic(args.workload, chains, args.steps if r["iterations_per_launch"] > 1 else 64,

@@ -2,8 +2,8 @@
 # Round-4 profile set, on the MI355X box: bash scratch/collect_r04.sh gpurun_out/r04
 export TMPDIR=/tmp
 out=$1; mkdir -p $out
-python3 bench.py > $out/bench_default.json 2> $out/bench_default.err < /dev/null || echo "bench default failed"
-python3 bench.py --steps 20 --warmup 5 > $out/bench_driver_args.json 2> $out/bench_driver_args.err < /dev/null || echo "bench driver args failed"
+python3 bench.py --full > $out/bench_default.json 2> $out/bench_default.err < /dev/null || echo "bench default failed"
+python3 bench.py --full --steps 20 --warmup 5 > $out/bench_driver_args.json 2> $out/bench_driver_args.err < /dev/null || echo "bench driver args failed"
 bash scratch/pmc_persist.sh $out/pmc > $out/pmc.log 2>&1
 bash scratch/pmc_persist_long.sh $out/pmc_long > $out/pmc_long.log 2>&1
 bash scratch/pmc_spec.sh $out/pmc_spec 10000 256 > $out/pmc_spec.log 2>&1

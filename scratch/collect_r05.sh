@@ -2,9 +2,9 @@
 # Round-5 profile set, on the MI355X box: bash scratch/collect_r05.sh gpurun_out/r05
 export TMPDIR=/tmp
 out=$1; mkdir -p $out
-LR_BENCH_DETAIL=$out/bench_default_detail.json python3 bench.py > $out/bench_default.out 2> $out/bench_default.err < /dev/null || echo "bench default failed"
+LR_BENCH_DETAIL=$out/bench_default_detail.json python3 bench.py --full > $out/bench_default.out 2> $out/bench_default.err < /dev/null || echo "bench default failed"
 tail -c 300 $out/bench_default.out; echo
-LR_BENCH_DETAIL=$out/bench_driver_args_detail.json python3 bench.py --steps 20 --warmup 5 > $out/bench_driver_args.out 2> $out/bench_driver_args.err < /dev/null || echo "bench driver args failed"
+LR_BENCH_DETAIL=$out/bench_driver_args_detail.json python3 bench.py --full --steps 20 --warmup 5 > $out/bench_driver_args.out 2> $out/bench_driver_args.err < /dev/null || echo "bench driver args failed"
 tail -c 300 $out/bench_driver_args.out; echo
 LR_BENCH_DETAIL=$out/pmc/stats_bench_detail.json bash scratch/pmc_persist.sh $out/pmc > $out/pmc.log 2>&1
 bash scratch/pmc_persist_long.sh $out/pmc_long > $out/pmc_long.log 2>&1

@@ -3,7 +3,7 @@
 
 Run in the build container only (needs /root/reference):
 
-    python tests/golden/make_golden.py [--only binning,proposals,ddrate,ratemaps,ddtraj,shipped,cfg1,trendtraj,traj,library,flags,marginal,parse]
+    python tests/golden/make_golden.py [--only binning,proposals,ddrate,ratemaps,ddtraj,shipped,cfg1,trendtraj,traj,library,flags,marginal,parse,signatures,ddbody]
     python tests/golden/make_chains.py <dataset> <model> <n> <s> <chains>   # long reference chains
 
 The reference is executed unmodified: LiteRateForward.py / DDRate.py through
@@ -723,6 +723,107 @@ def make_parse_paths(work):
     np.savez_compressed(os.path.join(HERE, "parse_paths.npz"), **out)
 
 
+def _import_reference_library(module_name="literate_library"):
+    import importlib.util
+    spec = importlib.util.spec_from_file_location(module_name, os.path.join(REF, "literate_library.py"))
+    ref = importlib.util.module_from_spec(spec)
+    sys.path.insert(0, REF)
+    try:
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            spec.loader.exec_module(ref)
+    finally:
+        sys.path.pop(0)
+    return ref
+
+
+def make_signatures(work):
+    """Parameter names and defaults of every public function of the reference's literate_library.py (the drop-in
+    module must offer the same call forms)."""
+    import inspect
+    import types
+    ref = _import_reference_library("ref_literate_library")
+    out = {}
+    for name, fn in vars(ref).items():
+        if isinstance(fn, types.FunctionType) and fn.__module__ == "ref_literate_library":
+            out[name] = [[p, v.default is not inspect.Parameter.empty,
+                          None if v.default is inspect.Parameter.empty else v.default]
+                         for p, v in inspect.signature(fn).parameters.items()]
+    with open(os.path.join(HERE, "library_signatures.json"), "w") as f:
+        json.dump(out, f, indent=0)
+    print("signatures:", len(out))
+
+
+def make_ddrate_body(work):
+    """The library calls the reference's DDRate.py makes with `-n 0` (its whole body up to the sampling loop: argument
+    parser, set_seed, parse_ts_te, create_bins, print_empirical_rates) and then in its calc_prior on one state, recorded
+    through a stand-in module that forwards every function of the reference's literate_library: per call the name, the
+    arguments and the result.  Arrays go into the npz, the call list as JSON (`record`); the data file's path is "@data".
+    Also recorded: the values of the body's globals the replay checks, calc_prior's value and its first call's index."""
+    import types
+    ref = _import_reference_library()
+    rel = DATASETS["metal_bands"][0]
+    dst = os.path.join(work, os.path.basename(rel))
+    shutil.copy(os.path.join(REF, rel), dst)
+    calls = []
+    proxy = types.ModuleType("literate_library")
+    for name, v in vars(ref).items():
+        if name.startswith("_"):
+            continue
+        if isinstance(v, types.FunctionType) and v.__module__ == ref.__name__:
+            def forward(*a, _fn=v, _name=name, **k):
+                r = _fn(*a, **k)
+                calls.append((_name, a, k, r))
+                return r
+            setattr(proxy, name, forward)
+        else:
+            setattr(proxy, name, v)
+    arrays, seen = {}, {}
+
+    def enc(x):
+        if isinstance(x, argparse.ArgumentParser):
+            return {"parser": True}
+        if isinstance(x, str):
+            return "@data" if x == dst else x
+        if isinstance(x, (list, tuple)):
+            return [enc(v) for v in x]
+        if isinstance(x, np.ndarray) and x.ndim > 0:
+            if id(x) not in seen:
+                seen[id(x)] = "a%d" % len(arrays)
+                arrays[seen[id(x)]] = x
+            return {"array": seen[id(x)]}
+        if isinstance(x, (np.generic, np.ndarray)):
+            x = x.item()
+        if x is None or isinstance(x, (bool, int, float)):
+            return x
+        raise TypeError(type(x))
+
+    argv = ["DDRate.py", "-d", dst, "-n", "0", "-seed", "3", "-m_birth", "2", "-m_death", "2"]
+    old_argv, old_mod = sys.argv, sys.modules.get("literate_library")
+    sys.argv, sys.modules["literate_library"] = argv, proxy
+    try:
+        with warnings.catch_warnings(), contextlib.redirect_stdout(io.StringIO()):
+            warnings.simplefilter("ignore")
+            g = runpy.run_path(os.path.join(REF, "DDRate.py"), run_name="__main__")
+            state = np.array([0.5, 1.5, 5.0, 10., 20000., 0.1, 1., 1.])
+            body_calls = len(calls)
+            prior = g["calc_prior"](state)
+    finally:
+        sys.argv = old_argv
+        if old_mod is None:
+            sys.modules.pop("literate_library", None)
+        else:
+            sys.modules["literate_library"] = old_mod
+    record = {"argv": ["@data" if a == dst else a for a in argv[1:]],
+              "args": {k: enc(v) for k, v in vars(g["args"]).items()},
+              "calls": [{"name": n, "args": enc(list(a)), "kwargs": {k: enc(v) for k, v in kw.items()}, "result": enc(r)}
+                        for n, a, kw, r in calls],
+              "globals": {k: enc(g[k]) for k in ("N_TIME_BINS", "PRIOR_K0_L", "ORIGIN", "PRESENT")},
+              "calc_prior_state": state.tolist(), "calc_prior": float(prior), "calc_prior_first_call": body_calls}
+    np.savez_compressed(os.path.join(HERE, "ddrate_body.npz"), record=np.array(json.dumps(record)), **arrays)
+    print("ddrate body:", [c[0] for c in calls], len(arrays), "arrays")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default="")
@@ -730,7 +831,7 @@ def main():
     work = tempfile.mkdtemp(prefix="lr_golden_")
     steps = dict(binning=make_binning_and_lik, proposals=make_proposals, ddrate=make_ddrate, ratemaps=make_ratemaps, ddtraj=make_dd_trajectories, shipped=make_shipped, cfg1=make_cfg1, trendtraj=make_trend_trajectories,
                  traj=make_trajectories, library=make_library_surface, flags=make_flag_paths, marginal=make_marginal_rates,
-                 parse=make_parse_paths)
+                 parse=make_parse_paths, signatures=make_signatures, ddbody=make_ddrate_body)
     for name, fn in steps.items():
         if args.only and name not in args.only.split(","):
             continue

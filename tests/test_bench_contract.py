@@ -239,3 +239,64 @@ def test_profile_summary_agrees_with_the_bench_line():
     b = json.load(open(os.path.join(ROOT, "profiles", "r04_bench_cfg4_1gpu.json")))
     assert p["kernel"].split("<")[0] == b["roofline"]["kernel"].split("<")[0] == d["kernel"].split("<")[0]
     assert 0 < p["lds_busy_fraction"] < 1 and 0 < p["valu_busy_fraction"] < 1
+
+
+def test_dump_outputs_writes_the_chain_states_as_finite_float64(tmp_path, monkeypatch):
+    """--dump-outputs: the accepted state of every chain (scalars per chain, the ragged rate / shift-time lists
+    concatenated chain after chain) and the region's last trace row split into its log columns and its sampled rates -
+    one float64 .npy per name, finite values only (nothing is padded); past the size bound a fixed seeded sample of the
+    chains, with its indices."""
+    import sys
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import bench
+    from literate_amd import _hip
+    K, W, H = _hip.LR_KMAX, _hip.LR_TRACE_W, _hip.LR_TRACE_HEAD
+
+    def snap(n):
+        rng = np.random.default_rng(n)
+        kl, km = rng.integers(1, K + 1, n), rng.integers(1, K + 1, n)
+        return dict(K_l=kl.astype(np.int32), K_m=km.astype(np.int32), L=[rng.random(x) for x in kl],
+                    M=[rng.random(x) for x in km], tL=[rng.random(x + 1) for x in kl], tM=[rng.random(x + 1) for x in km],
+                    likA=rng.random(n), priorA=rng.random(n), gamma_rate=rng.random((n, 2)), poi=rng.random(n),
+                    accepted=rng.integers(1, 99, n).astype(np.int32), it=np.full(n, 250, dtype=np.int64))
+
+    def trace(s):
+        # device rows: the head, then L / interior tL / M / interior tM in their K-wide slots; unused slots hold NaN here
+        n = len(s["L"])
+        t = np.full((n, W), np.nan)
+        for c in range(n):
+            kl, km = s["K_l"][c], s["K_m"][c]
+            t[c, :H] = np.arange(H) + c
+            t[c, 6], t[c, 7] = kl, km
+            t[c, H:H + kl] = s["L"][c]
+            t[c, H + K:H + K + kl - 1] = s["tL"][c][1:-1]
+            t[c, H + 2 * K - 1:H + 2 * K - 1 + km] = s["M"][c]
+            t[c, H + 3 * K - 1:H + 3 * K - 1 + km - 1] = s["tM"][c][1:-1]
+        return t
+
+    s = snap(64)
+    names = bench.dump_outputs(s, trace(s), str(tmp_path / "a"))
+    assert "chain_index" not in names and {"trace_head", "trace_sp", "trace_ex"} <= set(names)
+    got = {k: np.load(tmp_path / "a" / (k + ".npy")) for k in names}
+    assert all(a.dtype == np.float64 and np.all(np.isfinite(a)) for a in got.values())
+    assert np.array_equal(got["L"], np.concatenate(s["L"])) and np.array_equal(got["tM"], np.concatenate(s["tM"]))
+    assert len(got["tL"]) == int(s["K_l"].sum()) + 64 and np.array_equal(got["K_l"], s["K_l"].astype(float))
+    assert np.array_equal(got["it"], np.full(64, 250.0)) and np.array_equal(got["accepted"], s["accepted"].astype(float))
+    assert got["trace_head"].shape == (64, H) and got["trace_head"][5, 0] == 5
+    assert np.array_equal(got["trace_sp"], np.concatenate([np.concatenate([s["L"][c], s["tL"][c][1:-1]]) for c in range(64)]))
+    assert np.array_equal(got["trace_ex"], np.concatenate([np.concatenate([s["M"][c], s["tM"][c][1:-1]]) for c in range(64)]))
+    assert not {"trace_head", "trace_sp", "trace_ex"} & set(bench.dump_outputs(s, None, str(tmp_path / "b")))
+    # past the bound: a sample fixed by the chain count alone, and everything under the bound
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 200_000)
+    big = snap(300)
+    names = bench.dump_outputs(big, trace(big), str(tmp_path / "c"))
+    idx = np.load(tmp_path / "c" / "chain_index.npy").astype(int)
+    assert sum(os.path.getsize(tmp_path / "c" / (k + ".npy")) - 128 for k in names) <= 200_000
+    assert 0 < len(idx) < 300 and np.all(np.diff(idx) > 0)
+    assert np.array_equal(np.load(tmp_path / "c" / "likA.npy"), big["likA"][idx])
+    assert np.array_equal(np.load(tmp_path / "c" / "L.npy"), np.concatenate([big["L"][c] for c in idx]))
+    other = snap(300)
+    other["likA"] = other["likA"] + 1.0
+    bench.dump_outputs(other, None, str(tmp_path / "d"))
+    assert np.array_equal(np.load(tmp_path / "d" / "chain_index.npy"), idx)

@@ -365,7 +365,7 @@ def test_bench_two_rank_rehearsal_on_one_gpu():
     env.pop("WORLD_SIZE", None)
     # plain `python bench.py --gpus 2`, as the driver invokes it: bench.py starts its own two ranks (before touching the GPU)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "300", "--warmup", "50",
-           "--chains", "64", "--workload", "cfg3", "--no-cpu-baseline"]
+           "--chains", "64", "--workload", "cfg3", "--full", "--no-cpu-baseline"]
     out = subprocess.run(cmd, check=True, capture_output=True, text=True, timeout=300, env=env).stdout
     lines = [l for l in out.splitlines() if l.startswith("{")]
     assert len(lines) == 1                                  # rank 0 only
@@ -375,11 +375,42 @@ def test_bench_two_rank_rehearsal_on_one_gpu():
     assert b["n_gpus"] == 2 and b["config"]["chains_total"] == 128 and b["config"]["chains_per_gpu"] == 64
     assert b["scaling"] == "weak" and b["value"] > 0 and b["cpu_baseline"] is None
     assert b["value"] == pytest.approx(300 * b["config"]["lineages"] * 128 / (b["ms_per_step"] * 1e-3 * 300))
-    # the second leg of a multi-rank run: the same 64 chains IN TOTAL, sharded over the two ranks (strong scaling, the way
-    # BASELINE.json words cfg4: "1024 chains sharded across 8 GPUs")
+    # the second leg of a multi-rank run (--full): the same 64 chains IN TOTAL, sharded over the two ranks (strong scaling,
+    # the way BASELINE.json words cfg4: "1024 chains sharded across 8 GPUs")
     s = b["strong_scaling"]
     assert s["chains_total"] == 64 and s["chains_per_gpu"] == 32 and s["value"] > 0
     assert s["value"] == pytest.approx(300 * b["config"]["lineages"] * 64 / (s["ms_per_step"] * 1e-3 * 300))
+
+
+def test_bench_plain_run_times_the_steps_and_dumps_the_same_outputs_twice(tmp_path):
+    """A plain `bench.py --gpus 1` run times exactly --steps steps and measures nothing beside them (no CPU baseline, no
+    other configurations, no `abi`, no profiler traffic); --dump-outputs writes the chain states the last timed step left.
+    Inputs and seeds are fixed: two runs write the same states."""
+    import json
+    env = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "LR_DIST_BACKEND", "LR_SHARED_DEVICE"):
+        env.pop(k, None)
+    states = []
+    for run in ("a", "b"):
+        env["LR_BENCH_DETAIL"] = str(tmp_path / ("detail_%s.json" % run))
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "300", "--warmup", "50",
+               "--workload", "cfg3", "--chains", "64", "--sample-every", "10", "--dump-outputs", str(tmp_path / run)]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+        b = json.loads(r.stdout.rstrip().splitlines()[-1])
+        assert b["steps"] == 300 and b["warmup"] == 50 and b["ms_per_step"] > 0 and b["dtype"] == "f64"
+        assert b["value"] == pytest.approx(300 * b["config"]["lineages"] * 64 / (b["ms_per_step"] * 1e-3 * 300))
+        assert b["cpu_baseline"] is None and not {"configs", "co_headline", "abi", "strong_scaling"} & set(b)
+        assert b["roofline"]["traffic"] is None and b["config"]["trace_rows_gathered_in_region"] == 30
+        s = {f[:-4]: np.load(tmp_path / run / f) for f in os.listdir(tmp_path / run)}
+        assert all(a.dtype == np.float64 and np.all(np.isfinite(a)) for a in s.values())
+        assert np.all(s["it"] == 350) and s["likA"].shape == (64,) and len(s["L"]) == s["K_l"].sum()
+        assert s["trace_head"].shape == (64, 13) and np.all(s["trace_head"][:, 0] == 340)
+        assert len(s["trace_sp"]) == (2 * s["trace_head"][:, 6] - 1).sum()
+        states.append(s)
+    assert sorted(states[0]) == sorted(states[1])
+    for k in states[0]:
+        assert np.array_equal(states[0][k], states[1][k], equal_nan=True), k
 
 
 def _free_port():

@@ -1,22 +1,19 @@
 """CPU-side tests of the host surface around the hot loop, against fixtures made by RUNNING THE REFERENCE
-(tests/golden/make_golden.py --only library,flags,marginal):
+(tests/golden/make_golden.py --only library,flags,marginal,signatures,ddbody):
 
 * the literate_library.py names the reference's own callers import (priors, scalar proposals; lib:124-193);
 * the CLI flag paths -rev_se, -first_year / -last_year, -pyrate_output (LRF:324-341, 446-468);
 * get_marginal_rates (plotRJforward.v3.py:92-139), the definition of the posterior-parity metric;
-* the reference's DDRate.py body started against THIS repo's literate_library (star import, signatures).
+* the reference's DDRate.py body against THIS repo's literate_library (signatures; its library calls, recorded and replayed).
 """
 import inspect
 import json
 import os
-import sys
-import types
 
 import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference"
 
 
 @pytest.fixture(scope="module")
@@ -85,34 +82,22 @@ def test_library_star_import_surface():
     assert ns["sum"] is np.sum and ns["log"] is np.log
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="the reference tree is only present in the build container")
-def test_signatures_match_the_reference_module():
+def test_signatures_match_the_reference_module(golden_dir):
     """Every public function of the reference's literate_library.py exists here with the same parameter names and
-    defaults (the CLI-local forms live under other names: prior_gamma_LRF, Poisson_prior)."""
-    import warnings
+    defaults (the CLI-local forms live under other names: prior_gamma_LRF, Poisson_prior).  The reference's signatures
+    are recorded in tests/golden/library_signatures.json (make_golden.py --only signatures)."""
     import literate_library as ours
-    sys.path.insert(0, REF)
-    sys.dont_write_bytecode = True
-    try:
-        import importlib.util
-        spec = importlib.util.spec_from_file_location("ref_literate_library", os.path.join(REF, "literate_library.py"))
-        ref = importlib.util.module_from_spec(spec)
-        with warnings.catch_warnings():
-            warnings.simplefilter("ignore")
-            spec.loader.exec_module(ref)
-    finally:
-        sys.path.pop(0)
+    with open(os.path.join(golden_dir, "library_signatures.json")) as f:
+        ref = json.load(f)
     checked = 0
-    for name, fn in vars(ref).items():
-        if not isinstance(fn, types.FunctionType) or fn.__module__ != "ref_literate_library":
-            continue
+    for name, params in ref.items():
         assert hasattr(ours, name), name
-        a, b = inspect.signature(fn), inspect.signature(getattr(ours, name))
-        assert list(a.parameters) == list(b.parameters), (name, a, b)
-        for p in a.parameters:
-            da, db = a.parameters[p].default, b.parameters[p].default
-            assert (da is inspect._empty) == (db is inspect._empty), (name, p)
-            if da is not inspect._empty:
+        b = inspect.signature(getattr(ours, name))
+        assert [p for p, _, _ in params] == list(b.parameters), (name, params, b)
+        for p, has_default, da in params:
+            db = b.parameters[p].default
+            assert has_default == (db is not inspect._empty), (name, p)
+            if has_default:
                 assert np.all(da == db), (name, p, da, db)
         checked += 1
     assert checked >= 25
@@ -224,14 +209,15 @@ def test_marginal_rates_pinned_on_reference_get_marginal_rates(golden_dir):
         assert np.allclose(o[0], M[kind + "/mean"], rtol=1e-13) and np.array_equal(o[1], M[kind + "/hpd_lo"])
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="the reference tree is only present in the build container")
-def test_reference_ddrate_body_runs_on_this_library(tmp_path, monkeypatch):
+def test_reference_ddrate_body_runs_on_this_library(tmp_path, monkeypatch, golden_dir):
     """the reference's DDRate.py, unmodified, with THIS repo's literate_library first on the
-    path.  `-n 0` runs its whole body up to the sampling loop: the star import, parse_ts_te, create_bins, the initial
-    likelihood_function and calc_prior (prior_gamma(x, a=, s=, l=), prior_norm).  No GPU here, so the binning kernel
-    behind create_bins is stood in for by the oracle's (the checker); everything else is the product's host code."""
-    import runpy
-    import shutil
+    path.  tests/golden/ddrate_body.npz (make_golden.py --only ddbody) holds every library call its body makes with `-n 0`
+    - its whole body up to the sampling loop: the star import, core_arguments, set_seed, parse_ts_te, create_bins,
+    print_empirical_rates - and its calc_prior on one state (prior_gamma(x, a=, s=, l=), prior_norm), each with the
+    arguments it passed and the result the reference's library gave.  The calls are replayed in order on the names the
+    star import of this library hands over, on the same data file (written back from the recorded columns).  No GPU
+    here, so the binning kernel behind create_bins is stood in for by the oracle's (the checker); everything else is the
+    product's host code."""
     import literate_library as ll
     from literate_amd import ops
     from oracle import literate_oracle as lo
@@ -253,15 +239,59 @@ def test_reference_ddrate_body_runs_on_this_library(tmp_path, monkeypatch):
                 _T(np.array([r[2] for r in res], dtype=float)))
 
     monkeypatch.setattr(ops, "bin_events", fake_bin_events)
+    D = np.load(os.path.join(golden_dir, "ddrate_body.npz"))
+    rec = json.loads(str(D["record"]))
+    calls = rec["calls"]
+    # the shipped metal_bands_1.tsv as the body read it: four columns (clade, id, ts, te), whole years
+    parse = next(c for c in calls if c["name"] == "parse_ts_te")
+    ts_years = D[parse["result"][0]["array"]]
+    te_years = D[parse["result"][1]["array"]] - parse["args"][4]
     data = os.path.join(tmp_path, "metal_bands_1.tsv")
-    shutil.copy(os.path.join(REF, "example_data/metal_bands/single_run/metal_bands_1.tsv"), data)
-    monkeypatch.setattr(sys, "argv", ["DDRate.py", "-d", data, "-n", "0", "-seed", "3", "-m_birth", "2", "-m_death", "2"])
-    monkeypatch.setattr(sys, "path", [ROOT] + [p for p in sys.path if p != REF])
-    monkeypatch.setattr(sys, "dont_write_bytecode", True)
-    assert sys.modules.get("literate_library") is None or sys.modules["literate_library"].__file__.startswith(ROOT)
-    g = runpy.run_path(os.path.join(REF, "DDRate.py"), run_name="__main__")
-    assert g["create_bins"] is ll.create_bins and g["prior_gamma"] is ll.prior_gamma
-    # the body got as far as the initial state: its statistics are the golden ones of the oracle tests
-    assert g["N_TIME_BINS"] == len(g["DT"]) and g["PRIOR_K0_L"] == np.max(g["DT"])
-    p = g["calc_prior"](np.array([0.5, 1.5, 5.0, 10., 20000., 0.1, 1., 1.]))
-    assert np.isfinite(p)
+    with open(data, "w") as f:
+        f.write("clade\tband_id\tts\tte\n")
+        for i, (a, b) in enumerate(zip(ts_years, te_years)):
+            f.write("0\t%d\t%d\t%d\n" % (i, a, b))
+
+    def dec(x):
+        if isinstance(x, list):
+            return [dec(v) for v in x]
+        if isinstance(x, dict):
+            return D[x["array"]] if "array" in x else x
+        return data if x == "@data" else x
+
+    def same(got, want):
+        if isinstance(want, list):
+            assert len(got) == len(want)
+            return all(same(g, w) for g, w in zip(got, want))
+        if isinstance(want, dict):                  # the argument parser: checked through what it parses
+            return True
+        return np.array_equal(np.asarray(got), np.asarray(want)) or bool(np.allclose(got, want, rtol=1e-13, atol=0))
+
+    ns = {}
+    exec("from literate_library import *", ns)
+    assert ns["create_bins"] is ll.create_bins and ns["prior_gamma"] is ll.prior_gamma
+    out = {}
+    with np.errstate(all="ignore"):
+        for i, c in enumerate(calls):
+            fn = ns[c["name"]]
+            assert fn is getattr(ll, c["name"]), c["name"]
+            got = fn(*dec(c["args"]), **{k: dec(v) for k, v in c["kwargs"].items()})
+            assert same(got, dec(c["result"])), (i, c["name"])
+            out.setdefault(c["name"], got)
+    # the parser core_arguments builds reads the body's command line as the reference's did (the body adds its own three
+    # flags, -m_birth / -m_death / -fix_death, to it)
+    argv = [data if a == "@data" else a for a in rec["argv"]]
+    args, rest = out["core_arguments"].parse_known_args(argv)
+    assert rest == ["-m_birth", "2", "-m_death", "2"]
+    for k, v in rec["args"].items():
+        if k not in ("m_birth", "m_death", "fix_death"):
+            assert getattr(args, k) == dec(v), k
+    # the body got as far as the initial state: its globals follow from create_bins as the reference's did
+    origin, present, n_spec, n_exti, DT, n_time_bins, time_range = out["create_bins"]
+    g = rec["globals"]
+    assert n_time_bins == g["N_TIME_BINS"] == len(DT) and np.max(DT) == g["PRIOR_K0_L"]
+    assert origin == g["ORIGIN"] and present == g["PRESENT"]
+    priors = calls[rec["calc_prior_first_call"]:]              # calc_prior on the recorded state: a sum of priors
+    assert {c["name"] for c in priors} == {"prior_gamma", "prior_norm"}
+    p = sum(ns[c["name"]](*dec(c["args"]), **c["kwargs"]) for c in priors)
+    assert np.isfinite(p) and p == pytest.approx(rec["calc_prior"], rel=1e-13)
