@@ -91,7 +91,10 @@ __device__ inline double lr_build_tables_segments_wave(const lr_seg_scratch* sc,
     int sl0 = 0, sm0 = 0;
     while (sl0 + 1 < KL && sc->edge[0][sl0 + 1] <= b0) ++sl0;
     while (sm0 + 1 < KM && sc->edge[1][sm0 + 1] <= b0) ++sm0;
-    double sumR = 0.0, sumRl = 0.0, csum = 0.0;
+    // model 3 on one table class (the packed layouts of the persistent kernels and the packed scan, H = 520 included):
+    // the extant block behind the death-side entries, as lr_build_tables_segments_fast writes it
+    const bool ext = model == LR_MODEL_KEIDING_DEAD && n_cls == 1 && unit != LR_TAB_GENERAL;
+    double sumR = 0.0, sumRl = 0.0, sumM = 0.0, csum = 0.0;
     int sl = sl0, sm = sm0;
     for (int b = b0; b < b1; ++b) {
         while (sl + 1 < KL && sc->edge[0][sl + 1] <= b) ++sl;
@@ -103,11 +106,15 @@ __device__ inline double lr_build_tables_segments_wave(const lr_seg_scratch* sc,
         sumR += R;
         if (model >= 2) sumRl += lam;
         if (model == 1 && live) csum -= lam;
+        sumM += mu;
     }
-    double totR, totRl = 0.0;
+    double totR, totRl = 0.0, totM = 0.0;
     double cum = lr_wave_exclusive_scan(sumR, lane, &totR);
-    double cuml = 0.0;
+    double cuml = 0.0, cumM = 0.0;
     if (n_cls == 2) cuml = lr_wave_exclusive_scan(sumRl, lane, &totRl);
+    if (ext) cumM = lr_wave_exclusive_scan(sumM, lane, &totM);
+    const double totL = totR - totM;
+    const int x0 = H + n_bins + 2;
     sl = sl0, sm = sm0;
     for (int b = b0; b < b1; ++b) {
         while (sl + 1 < KL && sc->edge[0][sl + 1] <= b) ++sl;
@@ -131,10 +138,15 @@ __device__ inline double lr_build_tables_segments_wave(const lr_seg_scratch* sc,
             tab[3 * H + b + 1] = make_double2(-cuml, -lam);
             cuml += lam;
         }
+        if (ext) {
+            lr_put_S(tabd, unit, es, x0 + b + 1, -totL - cumM, -mu, fs0);
+            cumM += mu;
+        }
     }
     if (lane == 0) {
         lr_put_S(tabd, unit, es, 0, 0.0, 0.0, fs0), lr_put_E(tabd, unit, es, H, 0.0, 0.0, fe0);
         lr_put_S(tabd, unit, es, n_bins + 1, totR, 0.0, fs0), lr_put_E(tabd, unit, es, H + n_bins + 1, -totR, 0.0, fe0);
+        if (ext) lr_put_S(tabd, unit, es, x0, -totL, 0.0, fs0), lr_put_S(tabd, unit, es, x0 + n_bins + 1, -totR, 0.0, fs0);
         if (n_cls == 2) {
             tab[2 * H] = make_double2(0.0, 0.0);
             tab[3 * H] = make_double2(0.0, 0.0);
@@ -305,7 +317,9 @@ __device__ __forceinline__ double lr_build_tables_segments(const lr_seg_scratch*
                                                                     lane, unit, fs0, fe0, es, sg);
     // (run-time dispatch: the bins-per-lane count of the table size, as the kernels instantiated for H use it - every
     // builder of an engine then produces the same doubles for the same state, whichever kernel runs it)
-    if (n_cls == 1 && H <= 264) {
+    // (the one-pass builder holds LR_WAVE x lr_bins_per_lane(H) bins: the generic launch-based plan of 257 .. 262 bins has
+    // H = n_bins + 2 <= 264 but more bins than that, and takes the two-pass builder)
+    if (n_cls == 1 && H <= 264 && n_bins <= LR_WAVE * lr_bins_per_lane(H)) {
         switch (lr_bins_per_lane(H)) {
             case 1: return lr_build_tables_segments_fast<1>(sc, eL, eM, KL, KM, br_length, log_br, model, n_bins, H, tab, lane, unit, fs0, fe0, es, sg);
             case 2: return lr_build_tables_segments_fast<2>(sc, eL, eM, KL, KM, br_length, log_br, model, n_bins, H, tab, lane, unit, fs0, fe0, es, sg);

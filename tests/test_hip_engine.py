@@ -6,6 +6,8 @@ import os
 import numpy as np
 import pytest
 
+from helpers.edges import accepted_rates as _accepted_rates
+
 pytestmark = pytest.mark.gpu
 
 
@@ -911,13 +913,6 @@ def test_parametric_samplers_resume_and_sharding(G, golden_dir, tmp_path, kind):
     assert torch.equal(bits(shard.trace[:, 0]), bits(full.trace[:, 4])) and torch.equal(bits(shard.trace[:, 1]), bits(full.trace[:, 5]))
     for e in (full, b, shard):
         e.close()
-
-
-def _accepted_rates(snap, n_bins, C):
-    from oracle import literate_oracle as lo
-    lam = np.stack([snap["L"][c][lo.get_rate_index(np.floor(snap["tL"][c]), n_bins)] for c in range(C)])
-    mu = np.stack([snap["M"][c][lo.get_rate_index(np.floor(snap["tM"][c]), n_bins)] for c in range(C)])
-    return lam, mu
 
 
 @pytest.mark.parametrize("engine,C,team,n_lin", [("spec", 128, 4, 100_000), ("persistent4", 1024, 0, 100_000),
