@@ -48,6 +48,10 @@ def build_parser():
                    'resumed from if it exists (same data and flags; extension to the reference, which cannot resume)')
     p.add_argument('--combine', type=float, default=-1.0, help='with --chains > 1: also write COMBINED_{mcmc,sp_rates,'
                    'ex_rates,div}.log with this burn-in fraction dropped per chain (plotRJforward.v3.py combine_logs)')
+    p.add_argument('--rtt', type=float, default=-1.0, help='after the run, write <stem>_RTT.tsv (posterior mean and 95 %% HPD '
+                   'of the birth, death and net rates and the frequency of rate shifts per unit bin) and <stem>_RTT_K.tsv '
+                   '(histogram of the number of rates) next to the logs, pooled over all chains with this burn-in fraction '
+                   'dropped per chain (plotRJforward.v3.py -combine 1); computed on the GPU')
     p.add_argument('--init_shifts', type=int, default=0, help='initial number of rate shifts per process')
     p.add_argument('--block', type=int, default=0, help='iterations per device window: logs are written and flushed and '
                    'the state is printed once per window, while the next one runs (default: -p rounded up to ~50000)')
@@ -84,6 +88,11 @@ def parse_data(args):
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
+    if args.rtt >= 0 and args.pyrate_output:
+        raise SystemExit("--rtt bins the AD / TBP times of the logs; -pyrate_output flips them, which the reference's plot "
+                         "does not bin the same way: not supported together")
+    if args.rtt >= 1:
+        raise SystemExit("--rtt takes a burn-in fraction in [0, 1)")
     print("\n\n             LiteRate - 20200206 (MI355X engine)\n")
     import torch
     import torch.distributed as dist
@@ -201,9 +210,31 @@ def main(argv=None):
     if rank == 0 and n_samples and args.combine >= 0 and args.chains > 1:
         files = [logs.log_paths(args.d, model, args.out, c)[1]["mcmc"] for c in range(args.chains)]
         logs.combine_logs(files, os.path.dirname(files[0]), args.combine)
+    if args.rtt >= 0 and n_samples:
+        write_rtt(args, eng, n_local, world, rank)
     eng.close()
     if world > 1:
         dist.destroy_process_group()
+
+
+def write_rtt(args, eng, n_local, world, rank):
+    """--rtt: the posterior rates through time of the whole run, pooled over all chains (plotRJforward.v3.py -combine 1:
+    combine_logs drops int(burnin * S) rows of every chain, then burnin = 0) -> <stem>_RTT.tsv and <stem>_RTT_K.tsv on
+    rank 0.  The post-burn-in rows are gathered to rank 0's device once; the summary runs there (ops.rtt_summary)."""
+    from literate_amd import dist as lrd
+    from literate_amd import logs, ops
+    S = eng.samples_done()
+    burn = int(args.rtt * S)
+    local = eng.trace[burn:S][:, :n_local]
+    rows = lrd.gather_traces(local.contiguous(), args.chains) if world > 1 else local
+    if rank != 0:
+        return
+    res = ops.rtt_summary(rows, S - burn, eng.start_time, eng.end_time, burnin=0.0, pooled=True)
+    out_dir, paths = logs.log_paths(args.d, args.model_BDI, args.out)
+    stem = paths["div"][:-len("_div.log")]
+    logs.write_rtt_tables(stem, res.time, res.rates[0].cpu().numpy(), res.shift_freq[0].cpu().numpy(),
+                          res.k_counts[0].cpu().numpy())
+    print("posterior rates through time: %s_RTT.tsv, %s_RTT_K.tsv (%d samples)" % (stem, stem, res.n_samples))
 
 
 if __name__ == "__main__":

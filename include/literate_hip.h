@@ -178,6 +178,29 @@ int lr_simulate_bd(const double* lam_steps, const double* mu_steps, int32_t n_st
 int64_t lr_format_rows(const double* vals, const int64_t* row_start, int64_t n_rows, uint64_t int_cols, int32_t flags,
                        char* out, int64_t cap);
 
+/* ---- Posterior rates through time: the summary of a run (plotRJforward.v3.py get_marginal_rates :92-139,
+ * plot_net_rate :234-270, the shift histogram of get_r_plot :166-178, get_K_values :292-305, calcHPD :12-28) --------------
+ * trace: rows [n_chains x n_samples] in the trace layout below, row (sample s, chain c) at trace + (s * n_chains + c) *
+ * LR_TRACE_W - the engine's resident trace (its first n_samples slots) or rows a caller assembled.  start_age / end_age =
+ * a / b, the root_age / death_age columns.  Bins: edges np.arange(a, b), n_bins = ceil(b - a) - 1, which must equal
+ * int(b - a) (else LR_ERR_SIZE: b - a integer valued, where the reference breaks).  Burn-in (0 <= burnin < 1):
+ *   pooled = 0: one group per chain, each dropping its first min(int(burnin S), int(0.9 S)) rows (the script's default);
+ *   pooled = 1: one group, int(burnin S) rows dropped from every chain, the rest pooled chain after chain (-combine 1).
+ * A group of n samples needs n_in = round-half-even(0.95 n) >= 2 (else LR_ERR_SIZE; the reference raises).
+ * Outputs (G = 1 pooled, n_chains per chain; bins in ascending time, bin i ending at e_{i+1}):
+ *   rates      [G, 3 kinds (birth, death, net = birth - death), 3 (mean, HPD low, HPD high), n_bins] doubles;
+ *   shift_freq [G, 2 (birth, death), n_bins]: shift times in the bin / n (0 where the group sampled <= 1 shift time);
+ *   k_counts   [G, 2 (K_l, K_m), LR_KMAX] int64: rows with K = 1 .. LR_KMAX.
+ * The HPD ends are sample values; means are fixed-order sums over the sorted column / n; counts are exact.  A workspace
+ * smaller than lr_rtt_summary_workspace_bytes (the whole problem in one pass) makes the call work through the bins in
+ * chunks, down to one bin per chunk (LR_ERR_WORKSPACE below that), with the same results bit for bit.  The size query
+ * asks the current device (the sort's temporary storage depends on it): LR_ERR_STATE when there is none.               */
+int64_t lr_rtt_summary_workspace_bytes(int32_t n_samples, int32_t n_chains, double start_age, double end_age,
+                                       double burnin, int32_t pooled);
+int lr_rtt_summary(const double* trace, int32_t n_samples, int32_t n_chains, double start_age, double end_age,
+                   double burnin, int32_t pooled, double* rates, double* shift_freq, int64_t* k_counts,
+                   void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- A11: fused multi-chain RJMCMC --------------------------------------------------------
  * Replaces runMCMC (LRF:216-373) for n_chains independent chains.  Per iteration: one scan of
  * the lineage arrays scoring every chain's proposal, then one chain-step kernel (reduce,

@@ -441,6 +441,13 @@ class ChainEngine:
         """Trace rows written so far: iterations 0, s, 2 s, ... below `iterations` (LRF:321)."""
         return min(self.cfg.n_trace_slots, (self.iterations + self.cfg.s_freq - 1) // self.cfg.s_freq)
 
+    def rtt_summary(self, burnin=0.2, pooled=True, workspace_bytes=None):
+        """Posterior rates through time of the rows sampled so far, on the resident trace (ops.rtt_summary); also after
+        load() of a checkpoint, which restores the trace."""
+        self.check_status()
+        return ops.rtt_summary(self.trace, self.samples_done(), self.cfg.start_time, self.cfg.end_time, burnin, pooled,
+                               workspace_bytes)
+
     def trace_rows(self, n_samples=None):
         """Trace buffer as numpy [samples, chains, LR_TRACE_W] (see include/literate_hip.h)."""
         self.check_status()

@@ -425,3 +425,23 @@ def marginal_rates(rows, start_age, end_age, burnin=0.2):
     hpd = np.array([calcHPD(mat[:, i], 0.95) for i in range(mat.shape[1])])
     frames = (edges - abs(edges[1] - edges[0]) / 2.)[1:]
     return frames, mat.mean(axis=0), hpd[:, 0], hpd[:, 1], mat
+
+
+RTT_HEAD = ["time", "birth_rate", "birth_minHPD", "birth_maxHPD", "death_rate", "death_minHPD", "death_maxHPD", "net_rate",
+            "net_minHPD", "net_maxHPD", "birth_counts", "death_counts"]
+
+
+def write_rtt_tables(stem, time, rates, shift_freq, k_counts):
+    """<stem>_RTT.tsv: one line per unit bin in ascending time, the columns RTT_HEAD - the R vectors plotRJforward.v3.py
+    writes (get_r_plot :142-175, plot_net_rate :257-259); <stem>_RTT_K.tsv: n_rates, K_l, K_m (get_K_values :292-305).
+    rates [3 kinds, (mean, lo, hi), n_bins], shift_freq [2, n_bins], k_counts [2, LR_KMAX] (host arrays of one group of
+    ops.rtt_summary).  Numbers as str(float), as the logs write them."""
+    cols = [np.asarray(time, dtype=float)] + [rates[k, s] for k in range(3) for s in range(3)] + [shift_freq[0], shift_freq[1]]
+    with open(stem + "_RTT.tsv", "w") as f:
+        f.write("\t".join(RTT_HEAD) + "\n")
+        for i in range(len(cols[0])):
+            f.write("\t".join(str(float(c[i])) for c in cols) + "\n")
+    with open(stem + "_RTT_K.tsv", "w") as f:
+        f.write("n_rates\tK_l\tK_m\n")
+        for k in range(k_counts.shape[1]):
+            f.write("%d\t%d\t%d\n" % (k + 1, int(k_counts[0, k]), int(k_counts[1, k])))

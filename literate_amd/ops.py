@@ -4,6 +4,7 @@ Every function enqueues on torch's current HIP stream and raises if the HIP libr
 missing (no CPU path).  Shapes follow include/literate_hip.h.
 """
 import os
+from collections import namedtuple
 
 import numpy as np
 
@@ -374,6 +375,61 @@ def simulate_bd(n_start, n_steps, seed, lam_steps=None, mu_steps=None, mode=0, l
     if overflow:
         raise OverflowError("simulate_bd: more than %d lineages; pass a larger capacity" % capacity)
     return ts[:n], te[:n], trace
+
+
+RttSummary = namedtuple("RttSummary", "time rates shift_freq k_counts n_samples")
+RttSummary.__doc__ = """lr_rtt_summary's results.  time [n_bins] (host): bin centres in ascending time; rates [G, 3, 3, n_bins]:
+(birth, death, net) x (mean, HPD low, HPD high); shift_freq [G, 2, n_bins]; k_counts int64 [G, 2, LR_KMAX] (K = 1 ..
+LR_KMAX); n_samples: samples per group.  G = 1 pooled, one per chain otherwise.  Device tensors, bins aligned with time."""
+
+
+def rtt_time(start_age, end_age):
+    """The bin centres get_marginal_rates returns (plotRJforward.v3.py:129-130): edges np.arange(a, b), e_{i+1} - 0.5."""
+    edges = np.arange(start_age, end_age)
+    if edges.size < 2:
+        return np.zeros(0)
+    return (edges - abs(edges[1] - edges[0]) / 2.)[1:]
+
+
+def rtt_summary(trace, n_samples, start_age, end_age, burnin=0.2, pooled=True, workspace_bytes=None):
+    """Posterior rates through time from trace rows [>= n_samples, C, LR_TRACE_W] (lr_rtt_summary: get_marginal_rates,
+    plot_net_rate, get_r_plot's shift histogram and get_K_values of plotRJforward.v3.py) -> RttSummary.
+    start_age / end_age: the root_age / death_age columns.  pooled: the rows of every chain pooled after dropping
+    int(burnin S) of each (-combine 1); else one summary per chain (burn-in capped at 0.9 S).  workspace_bytes: cap the
+    workspace (the call then works through the bins in chunks; the same results)."""
+    torch = _torch()
+    lib = _hip.load()
+    trace = _dev(trace, torch.float64)
+    if trace.dim() != 3 or trace.shape[2] != _hip.LR_TRACE_W or trace.shape[0] < int(n_samples):
+        raise ValueError("trace must be [>= n_samples, chains, LR_TRACE_W]")
+    S, C = int(n_samples), int(trace.shape[1])
+    a, b = float(start_age), float(end_age)
+    full = lib.lr_rtt_summary_workspace_bytes(S, C, a, b, float(burnin), int(bool(pooled)))
+    if full < 0:
+        _hip.check(int(full), "lr_rtt_summary_workspace_bytes")
+    time = rtt_time(a, b)
+    nb = time.size
+    G = 1 if pooled else C
+    dev = trace.device
+    rates = torch.empty((G, 3, 3, nb), dtype=torch.float64, device=dev)
+    freq = torch.empty((G, 2, nb), dtype=torch.float64, device=dev)
+    kc = torch.empty((G, 2, _hip.LR_KMAX), dtype=torch.int64, device=dev)
+    # by default at most a quarter of the free device memory (and never less than 1 GiB): the sort of a chunk's columns
+    # runs a block per column, so the more columns a pass holds, the more CUs it keeps busy (a thousand chains pooled over
+    # 123 bins: 7.3 GB in one pass)
+    if workspace_bytes is not None:
+        cap = int(workspace_bytes)
+    elif os.environ.get("LR_RTT_WORKSPACE"):
+        cap = int(os.environ["LR_RTT_WORKSPACE"])
+    else:
+        cap = max(1 << 30, torch.cuda.mem_get_info(dev)[0] // 4)
+    ws = torch.empty(max(1, min(int(full), cap)), dtype=torch.uint8, device=dev)
+    rc = _hip.launch(lib.lr_rtt_summary, dev, _hip.ptr(trace), S, C, a, b, float(burnin), int(bool(pooled)), _hip.ptr(rates),
+                     _hip.ptr(freq), _hip.ptr(kc), _hip.ptr(ws), ws.numel())
+    _hip.check(rc, "lr_rtt_summary")
+    burn = int(burnin * S)
+    per = S - (burn if pooled else min(burn, int(0.9 * S)))
+    return RttSummary(time, rates, freq, kc, per * C if pooled else per)
 
 
 def debug_draws(seed, chain, it, purpose, idx, kind, shape):
