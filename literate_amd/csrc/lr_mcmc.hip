@@ -218,16 +218,6 @@ __global__ __launch_bounds__(256) void lr_pairscan_kernel(lr_packed_lineages pk,
 // not add to the scan loop's, and both fit the 128-VGPR budget of 4 waves per SIMD.
 // Every pointer is LDS-typed: the argument block (copied to LDS once per launch; reading it through the generic pointer
 // to global memory costs an L2 round trip per field), the per-wave scratch, the state rows and the pair table.
-#ifndef LR_P4_STEPPER_DRAWS
-#define LR_P4_STEPPER_DRAWS 0   /* helper form, 1: a stepper makes the draws of its chain's NEXT step itself, behind its step
-                                   (measured: cfg4 6.66 us per iteration against 6.36 - EXPERIMENTS.md, round 5) */
-#endif
-#ifndef LR_P4_LAST_SUMS
-#define LR_P4_LAST_SUMS 1    /* four-chain kernel: the last scanner wave to finish reduces the block's scan sums */
-#endif
-#ifndef LR_P4_DRAW_AHEAD
-#define LR_P4_DRAW_AHEAD 1   /* four-chain kernel: the RJ sampler's draws are made one phase ahead by scanner waves */
-#endif
 typedef __attribute__((address_space(3))) double lr_lds_f64;
 typedef __attribute__((address_space(3))) int lr_lds_i32;
 // PB: bins per lane of the one-pass table builder for the kernel's table size (0: choose at run time), ES: the builders'
@@ -264,22 +254,6 @@ __device__ __forceinline__ void lr_persist_step_body(const __attribute__((addres
     LR_SSTAMP(8);
 }
 
-// The four-chain kernel's chain step that speculates on rejection (lr_chain_step_respec): the chain's two scratch / hand-over /
-// draw slots (parity of the iteration a proposal is for) and its staged candidate Q live in LDS beside the state rows.
-template <int PB>
-__device__ __forceinline__ void lr_persist_step_respec(const __attribute__((address_space(3))) lr_step_args* a3, int c, int lane,
-                                                       __attribute__((address_space(3))) lr_seg_scratch* scratch2,
-                                                       lr_lds_f64* st_f64, lr_lds_i32* st_i32, double lik, lr_lds_f64* br3,
-                                                       const lr_draw_slot* draws2, lr_table_hand* hands2, lr_pend* pend2, bool first,
-                                                       int epoch) {
-    const lr_step_args& a = *(const lr_step_args*)a3;
-    const double* br_lds = (const double*)br3;
-    LR_SSTAMP(0);
-    lr_chain_step_respec<PB>(a, c, lane, lik, (double*)st_f64, (int*)st_i32, pend2, (lr_seg_scratch*)scratch2, hands2, draws2, first,
-                             epoch, br_lds, br_lds + LR_H_WIDE);
-    LR_SSTAMP(8);
-}
-
 // End of a wave's share of scan number `scans_done` in the four-chain kernel: the lanes' sums into slot `slot` of
 // `part`, count in, and - the wave that arrives LAST of the NA scanning waves - add the block's sums up, per lane over the
 // slots in slot order, then across the lanes (the same order whoever is last), into out[0..1].
@@ -312,39 +286,6 @@ __device__ __attribute__((noinline)) void lr_persist_step(const __attribute__((a
     lr_persist_step_body<PB, ES>(a3, c, lane, scratch3, st_f64, st_i32, lik, table3, br3);
 }
 
-// ---- FLOW (-DLR_P4_FLOW=1; helper form): the phases of the four-chain kernel without their block-wide barrier -------------
-// In-kernel stamps of the step-less kernel (profiles/r05_p4_wave_stamps.txt): the twelve scanner waves of a phase start
-// together behind the barrier, the oldest are done after 1.9-2.2 us, the youngest after 2.5-2.65, the wave that arrives last
-// adds the block's sums (~0.3 us), then 0.3-0.5 us of barrier - about 1 us of a 3.15 us phase is waiting for one another.
-// Here every role runs on what it really needs:
-//   a scanning wave starts the scan of pair p's proposal q when both columns of its table stand (tab_epoch[p] >= 2 (q + 1));
-//   the wave that arrives LAST at the end of that scan (arrived[p] == NA (q + 1)) adds the sums and publishes sums_epoch[p] = q + 1;
-//   a stepper decides proposal q of its chain when sums_epoch[p] >= q + 1; its helper builds proposal q + 1's column behind
-//   the hand-over and bumps tab_epoch[p].
-// No wait can cycle: a wave finishes scan (p, q) before it waits for (p, q + 1), whose table needs the step that needs the
-// sums of (p, q).  The sums are added in slot order by whoever is last: the same doubles as with barriers.  A wait that
-// does not end within ~0.25 s raises the engine's status word and ends the launch (every other wait then ends too).
-#ifndef LR_P4_FLOW
-#define LR_P4_FLOW 0
-#endif
-struct lr_p4_flow_lds {
-    double2 part[2][14][LR_WAVE];                                // [pair][scanning wave][lane]: the lanes' sums of the pair's current scan
-    int arrived[2], sums_epoch[2], tab_epoch[2];
-    int abort, pad_;
-};
-__device__ __forceinline__ bool lr_flow_wait(const int* flag, int target, int* abort) {
-    for (unsigned int spins = 0;; ++spins) {
-        if (__hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) >= target) break;
-        if (spins > (1u << 21) || __hip_atomic_load(abort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != 0) {
-            __hip_atomic_store(abort, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            return false;
-        }
-        __builtin_amdgcn_s_sleep(2);
-    }
-    asm volatile("" ::: "memory");
-    return true;
-}
-
 // The stepper waves' whole launch in the four-chain kernel as ONE call: a call per step costs the callee-saved
 // registers' round trip through scratch memory every time (24 dwords x 64 lanes out and back: 0.5 + 0.2 us of a 3.6 us
 // step, measured with in-kernel stamps), a call per launch costs it once.  The function keeps the step's own register
@@ -353,19 +294,15 @@ __device__ __forceinline__ bool lr_flow_wait(const int* flag, int target, int* a
 //   st_f64 / st_i32: the four chains' state rows; red: [pair][wave][chain of the pair] scan sums; tab: the two pair
 //   tables, tab_doubles apart
 //   HELP: waves 2, 3 are helper waves - hands[wave] is this stepper's hand-over to wave 2 + wave (lr_persist4_kernel)
-//   SPEC: the step speculates on rejection (lr_chain_step_respec) - scratch3 / draws / hands are then [chain of the block][parity]
-//   and pend [chain of the block][parity]
-template <int PB, int ES, int NW, int SAMPLER, bool HELP, bool SPEC = false, bool FLOW = false>
+template <int PB, int ES, int NW, int SAMPLER, bool HELP>
 __device__ __attribute__((noinline)) void lr_persist4_steppers(const __attribute__((address_space(3))) lr_step_args* a3, int c0,
                                                                int n_chains, int wave, int lane,
                                                                __attribute__((address_space(3))) lr_seg_scratch* scratch3,
                                                                lr_lds_f64* st_f64, lr_lds_i32* st_i32, lr_lds_f64* red,
                                                                lr_lds_f64* tab, int tab_doubles, lr_lds_f64* br3, long long n_iters,
                                                                const lr_draw_slot* draws /* [4]: made ahead (RJ sampler) */,
-                                                               lr_table_hand* hands /* [2] */, lr_pend* pend = nullptr,
-                                                               lr_p4_flow_lds* fl = nullptr) {
-    static_assert(!HELP || (LR_P4_DRAW_AHEAD != 0 && ES == 2 && SAMPLER == 0), "helper waves: RJ sampler at unit resolution");
-    static_assert(!SPEC || HELP, "speculation on rejection: the form with helper waves");
+                                                               lr_table_hand* hands /* [2] */) {
+    static_assert(!HELP || (ES == 2 && SAMPLER == 0), "helper waves: RJ sampler at unit resolution");
     for (long long iter = 0; iter < n_iters; ++iter) {
 #pragma unroll 1
         for (int ph = 0; ph < 2; ++ph) {
@@ -373,42 +310,19 @@ __device__ __attribute__((noinline)) void lr_persist4_steppers(const __attribute
             const unsigned long long dq0 = wall_clock64();
 #endif
             const int c = c0 + 2 * ph + wave;
-            // FLOW: the sums of this pair's scan number `iter` instead of a barrier
-            if (FLOW && !lr_flow_wait(&fl->sums_epoch[ph], (int)iter + 1, &fl->abort)) return;
-#ifdef LR_P4_NOSTEP
-            if (false) {        // (timing experiment: the phases without their chain steps - the scan alone; results are void)
-#else
             if (c < n_chains) {
-#endif
                 double lik = 0.0;
 #pragma unroll
-                for (int w2 = 2; w2 < (LR_P4_LAST_SUMS != 0 && ES == 2 /* unit resolution: the block's sums in slot 2 */ ? 3 : NW); ++w2) lik += red[(ph * NW + w2) * 2 + wave];
-                if (SPEC) {
-                    const int ch = 2 * ph + wave;
-                    lr_persist_step_respec<(PB > 0 ? PB : 1)>(a3, c, lane, scratch3 + 2 * ch, st_f64 + ch * (LR_STATE_ROWS * LR_ROW),
-                                                st_i32 + ch * (LR_ISTATE_ROWS * LR_ROW), lik, br3, draws + 2 * ch, hands + 2 * ch,
-                                                pend + 2 * ch, iter == 0, (int)((2 * iter + ph + 1) & 0x3fffffff));
-                } else
-                lr_persist_step_body<PB, ES, LR_P4_DRAW_AHEAD != 0 && ES == 2 /* unit resolution */ && SAMPLER == 0, SAMPLER, HELP>(
+                for (int w2 = 2; w2 < (ES == 2 /* unit resolution: the block's sums in slot 2 */ ? 3 : NW); ++w2) lik += red[(ph * NW + w2) * 2 + wave];
+                lr_persist_step_body<PB, ES, ES == 2 /* unit resolution: draws made ahead */ && SAMPLER == 0, SAMPLER, HELP>(
                     a3, c, lane, scratch3, st_f64 + (2 * ph + wave) * (LR_STATE_ROWS * LR_ROW),
                     st_i32 + (2 * ph + wave) * (LR_ISTATE_ROWS * LR_ROW), lik, tab + ph * tab_doubles + wave, br3,
                     draws + (2 * ph + wave), HELP ? hands + wave : nullptr, (int)((2 * iter + ph + 1) & 0x3fffffff));
-                if (HELP && !SPEC && LR_P4_STEPPER_DRAWS) {
-                    // (experiment, off) The state-independent draws of this chain's NEXT step (iteration IT + 1, used two
-                    // phases on) by the stepper itself, which is done 1.7 us into a 3.15 us phase: on the scanner waves 4, 5
-                    // the Philox call sits BEHIND their scans (the four-chain kernel with its steps compiled out: 3.53 us per
-                    // phase with the draws, 2.97 without).  Same (iteration, purpose, index) addresses: the stream does not
-                    // change - and cfg4 runs 5 % SLOWER: more work on the steppers' SIMDs, once more.
-                    const int* Ic = (const int*)(st_i32 + (2 * ph + wave) * (LR_ISTATE_ROWS * LR_ROW)) + LR_IROW_SCALARS * LR_ROW;
-                    LR_WAVE_LDS_ORDER();
-                    const unsigned long long itn = ((unsigned long long)(unsigned int)Ic[LR_I_IT_HI] << 32 | (unsigned int)Ic[LR_I_IT_LO]) + 1ull;
-                    lr_spec_draw_both(*(const lr_step_args*)a3, c, lane, itn, const_cast<lr_draw_slot*>(draws) + (2 * ph + wave));
-                }
             }
 #ifdef LR_DIAG
             const unsigned long long dq1 = wall_clock64();
 #endif
-            if (!FLOW) __syncthreads();
+            __syncthreads();
 #ifdef LR_DIAG
             if (lane == 0 && blockIdx.x < 64) {
                 atomicAdd(&lr_diag_step[16384 + (blockIdx.x * 16 + wave) * 4 + 0], dq1 - dq0);
@@ -570,15 +484,6 @@ __global__ __launch_bounds__(T, LR_PERSIST_MINWAVES) void lr_persist_kernel(
 #ifndef LR_P4_THREADS
 #define LR_P4_THREADS 1024
 #endif
-#ifndef LR_P4_UNROLL
-#define LR_P4_UNROLL 1
-#endif
-#ifndef LR_P4_AGE_PRIO
-#define LR_P4_AGE_PRIO 0
-#endif
-#ifndef LR_P4_DRAW_WAVE
-#define LR_P4_DRAW_WAVE 2    /* SPEC form: first of the two scanner slots (wave 4 + slot) that make the draws ahead */
-#endif
 #ifdef LR_DIAG
 #define LR_PSTAMP(k) if (threadIdx.x == 0 && blockIdx.x < 64) lr_diag_step[28672 + blockIdx.x * 8 + (k)] = wall_clock64()
 #else
@@ -592,29 +497,14 @@ __global__ __launch_bounds__(T, LR_PERSIST_MINWAVES) void lr_persist_kernel(
 // and every SIMD carries one wave of the step and three scanners.  Before the hand-over arrives a helper scores the first
 // groups of the scan (sh.help_trips trips of the 128 helper lanes; the scanners stride over the rest), and the draws of the
 // OTHER pair's next step are one Philox call on each of the two oldest scanner waves (four waves, a call each, otherwise).
-// dynamic LDS of the SPEC form
-struct lr_p4_spec_lds {
-    lr_seg_scratch scratch[8];
-    lr_draw_slot draws[8];
-    lr_pend pend[8];
-    lr_table_hand hands[8];
-};
-
-#define LR_P4_SPEC_LDS_BYTES ((sizeof(lr_p4_spec_lds) + 255) / 256 * 256)      /* the FLOW arrays follow the SPEC ones in dynamic LDS */
-
-// SPEC (with HELP): the steppers speculate on REJECTION (lr_chain_step_respec, lr_step.h): the proposal a chain makes next
-// if its pending one is rejected is staged one iteration early, so that a helper starts the table build at the DECISION
-// (~0.4 us into a phase) instead of after move + staging (~1.2 us); scratch, hand-over and draw slots are then per chain
-// and parity of the iteration, the draws are made two iterations ahead.
 template <int H, bool GENERAL, bool PARAM /* a parametric sampler's chain step (DDRate, trend_rate) instead of the RJ sampler's */,
-          bool HELP = false, bool SPEC = false>
+          bool HELP = false>
 __global__ __launch_bounds__(LR_P4_THREADS, LR_P4_THREADS / 256) void lr_persist4_kernel(const lr_step_args* __restrict__ ap /* in global memory: a by-value argument struct measured
                                                                        0.2 us per launch faster, but one instantiation then kept a copy of it in scratch
                                                                        memory and read its fields from there in every phase */,
                                                                        lr_packed_lineages pk, long long n8,
                                                                        lr_p4_shares sh, long long n_iters, char* carry_all) {
     static_assert(!HELP || (!GENERAL && !PARAM), "helper waves: RJ sampler at unit resolution");
-    static_assert(!SPEC || HELP, "speculation on rejection: the form with helper waves");
     const lr_step_args& a = *ap;
     LR_PSTAMP(0);      // entry (LR_DIAG: wall-clock stamps of a launch's stages, blocks < 64; scratch/diag_p4_launch.py)
     constexpr int NW = LR_P4_THREADS / LR_WAVE;          // 16 waves: 2 steppers + 14 scanners (HELP: 2 + 2 helpers + 12)
@@ -629,22 +519,11 @@ __global__ __launch_bounds__(LR_P4_THREADS, LR_P4_THREADS / 256) void lr_persist
     // have left theirs: the wave that arrives LAST adds them up (one wave's reduction instead of fourteen: the kernel is
     // bound by instruction issue) - per lane over the waves in wave order, then across the lanes: the same order whoever
     // is last.  (On general times the scans are the longer side of a phase and the serial tail costs more than it saves.)
-    constexpr bool LAST_SUMS = LR_P4_LAST_SUMS != 0 && !GENERAL;
+    constexpr bool LAST_SUMS = !GENERAL;
     __shared__ double2 part[LAST_SUMS ? NW - 2 : 1][LR_WAVE];
     __shared__ int arrived;
-    // SPEC: hand-over, scratch, draw slots [chain][parity of the iteration the proposal is for] and the staged candidates live in
-    // DYNAMIC LDS (lr_p4_spec_lds, behind everything static): the pair tables must stay where a ds_read's 16-bit offset
-    // field reaches them - placed behind 45 KB more of static arrays their base no longer folded into the gathers, and the
-    // scan loop grew eight address adds per trip
-    __shared__ lr_table_hand hands_s[SPEC ? 1 : 2];
-    __shared__ lr_seg_scratch scratch_s[SPEC ? 1 : 2];
-    extern __shared__ double2 p4_dyn[];
-    lr_p4_spec_lds* const xs = reinterpret_cast<lr_p4_spec_lds*>(p4_dyn);
-    lr_table_hand* const hands = SPEC ? xs->hands : hands_s;
-    lr_seg_scratch* const scratch = SPEC ? xs->scratch : scratch_s;
-    lr_pend* const pend = xs->pend;
-    constexpr bool FLOW = LR_P4_FLOW != 0 && HELP;                   // (the phases without their barrier: lr_p4_flow_lds)
-    lr_p4_flow_lds* const fl = reinterpret_cast<lr_p4_flow_lds*>(reinterpret_cast<char*>(p4_dyn) + (SPEC ? LR_P4_SPEC_LDS_BYTES : 0));
+    __shared__ lr_table_hand hands[2];                    // HELP: stepper k's hand-over to helper wave 2 + k
+    __shared__ lr_seg_scratch scratch[2];                 // stepper k's scratch (HELP: the segments it hands over)
     __shared__ double st_f64[4][LR_STATE_ROWS * LR_ROW];
     __shared__ int st_i32[4][LR_ISTATE_ROWS * LR_ROW];
     __shared__ lr_step_args a_lds;
@@ -654,8 +533,10 @@ __global__ __launch_bounds__(LR_P4_THREADS, LR_P4_THREADS / 256) void lr_persist
     // finish first: the steppers are the kernel's critical path (one wave's instruction stream per chain step), the
     // scanners of a phase wait 1-2 us at its barrier.  Same (iteration, purpose, index) Philox addresses as the draws
     // made inside the step: the stream does not change.  RJ sampler only; the parametric samplers draw in the step.
-    __shared__ lr_draw_slot draws_s[SPEC ? 1 : 4];
-    lr_draw_slot* const draws = SPEC ? xs->draws : draws_s;
+    // (Reached through a pointer that draw_duty captures: with the array itself the inliner also takes prologue_draws
+    // into the kernels without helper waves, and their stepper functions then save callee-saved registers in scratch.)
+    __shared__ lr_draw_slot draws_s[4];
+    lr_draw_slot* const draws = draws_s;
     const int tid = threadIdx.x, lane = tid & (LR_WAVE - 1), wave = tid / LR_WAVE;
     if (tid < (int)(sizeof(lr_step_args) / 4)) reinterpret_cast<int*>(&a_lds)[tid] = reinterpret_cast<const int*>(ap)[tid];
     for (int b = tid; b < LR_H_WIDE; b += blockDim.x) {
@@ -664,67 +545,37 @@ __global__ __launch_bounds__(LR_P4_THREADS, LR_P4_THREADS / 256) void lr_persist
         br_lds[1][b] = in ? ap->log_br[b] : 0.0;
     }
     // (unit resolution only: on general times the scan loops are the longer side of a phase and have nothing to spare)
-    constexpr bool draw_ahead = LR_P4_DRAW_AHEAD && !GENERAL && !PARAM;
+    constexpr bool draw_ahead = !GENERAL && !PARAM;
     // draw duty of scanner wave 2 + q, q < 4, for the pair `pr` that has just been scanned: part q >> 1 of chain q & 1
-    // (SPEC: `ahead` iterations beyond the pending one - 2 in the loop, 1 and 2 in the prologue -, by scanner waves
-    // qoff, qoff + 1, into the slot of that iteration's parity)
     // (HELP: waves 4, 5 - the oldest scanners - sit on the steppers' SIMDs and end their scans last of all scanners (in-kernel
     // stamps: 3.1 us of a 3.15 us phase against 2.2-2.9 for the others) - and still the draws cost least there: by waves 6, 7
-    // (SIMDs 2, 3, beside the helpers) cfg4 ran 6.37-6.40 us per iteration against 6.25, A/B twice on one box; under SPEC, whose
-    // helpers build early, the other way round: 7.05 against 6.87)
-    auto draw_duty = [&](int pr, int ahead = SPEC ? 2 : 1, int qoff = SPEC ? LR_P4_DRAW_WAVE : 0, unsigned long long it_given = 0ull) {
-        const int q = wave - W0 - qoff, k = q & 1, ch = 2 * pr + k;      // (the oldest scanner waves: the first to finish)
+    // (SIMDs 2, 3, beside the helpers) cfg4 ran 6.37-6.40 us per iteration against 6.25, A/B twice on one box)
+    auto draw_duty = [&](int pr) {
+        const int q = wave - W0, k = q & 1, ch = 2 * pr + k;      // (the oldest scanner waves: the first to finish)
         if (!draw_ahead || q < 0 || q >= (HELP ? 2 : 4) || (int)(blockIdx.x * 4) + ch >= ap->cfg.n_chains) return;
-#if defined(LR_P4_NOSTEP) && LR_P4_NOSTEP >= 2
-        return;                    // (timing experiment: not even the draws)
-#endif
         const int* I = st_i32[ch] + LR_IROW_SCALARS * LR_ROW;
-        // (FLOW: the iteration is given - the state row of a chain may still be in its stepper's hands)
-        const unsigned long long it = it_given ? it_given
-                                               : ((unsigned long long)(unsigned int)I[LR_I_IT_HI] << 32 | (unsigned int)I[LR_I_IT_LO]) + (unsigned long long)ahead;
-        lr_draw_slot* slot = SPEC ? &draws[2 * ch + (int)(it & 1ull)] : &draws[ch];
+        const unsigned long long it = ((unsigned long long)(unsigned int)I[LR_I_IT_HI] << 32 | (unsigned int)I[LR_I_IT_LO]) + 1ull;
+        lr_draw_slot* slot = &draws[ch];
         // (HELP: one wave per chain, one Philox call for both parts)
         if (HELP) lr_spec_draw_both(a_lds, (int)(blockIdx.x * 4) + ch, lane, it, slot);
         else lr_spec_draw_part(a_lds, (int)(blockIdx.x * 4) + ch, lane, it, slot, q >> 1);
     };
     // a helper wave's table duty of a phase whose steppers advance pair `ph`: once the stepper has handed them over, the
     // tables of its chain of pair ph
-    // (SPEC: the slots of the chain's NEW pending iteration, it0 + iter + 1 - `par`)
-    auto help_duty = [&](int ph, int epoch, int par = 0) {
+    auto help_duty = [&](int ph, int epoch) {
         const int k = wave - 2;
         const int ch = 2 * ph + k;
-        // (FLOW: a column that is not built - no such chain - still counts as standing)
-        auto column_stands = [&]() {
-            if (FLOW) {
-                LR_WAVE_LDS_ORDER();
-                if (lane == 0) __hip_atomic_fetch_add(&fl->tab_epoch[ph], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            }
-        };
-        if ((int)(blockIdx.x * 4) + ch >= ap->cfg.n_chains) { column_stands(); return; }
-#ifdef LR_P4_NOSTEP
-        column_stands();
-        return;
-#endif
-        lr_table_hand* hand = SPEC ? &hands[2 * ch + par] : &hands[k];
+        if ((int)(blockIdx.x * 4) + ch >= ap->cfg.n_chains) return;
+        lr_table_hand* hand = &hands[k];
 #ifdef LR_DIAG
         const unsigned long long dh0 = wall_clock64();
 #endif
-        if (FLOW) {
-            // (bounded, and ended by any other wait's time-out: a stepper that gave up hands nothing over)
-            for (unsigned int spins = 0; __hip_atomic_load(&hand->epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != epoch; ++spins) {
-                if (spins > (1u << 21) || __hip_atomic_load(&fl->abort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != 0) {
-                    __hip_atomic_store(&fl->abort, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    return;
-                }
-                __builtin_amdgcn_s_sleep(1);
-            }
-        } else
         while (__hip_atomic_load(&hand->epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != epoch) __builtin_amdgcn_s_sleep(1);
         asm volatile("" ::: "memory");
 #ifdef LR_DIAG
         if (lane == 0 && blockIdx.x < 64) atomicAdd(&lr_diag_step[16384 + (blockIdx.x * 16 + wave) * 4 + 2], wall_clock64() - dh0);
 #endif
-        const lr_seg_scratch* sc = SPEC ? &scratch[2 * ch + par] : &scratch[k];
+        const lr_seg_scratch* sc = &scratch[k];
         const int eL = lane <= LR_KMAX ? sc->edge[0][lane] : 0, eM = lane <= LR_KMAX ? sc->edge[1][lane] : 0;
         double* tabd = reinterpret_cast<double*>(tab[ph]) + k;
         const double constP = lr_build_tables_segments<(H <= 264 ? lr_bins_per_lane(H) : 1), 2>(
@@ -732,14 +583,10 @@ __global__ __launch_bounds__(LR_P4_THREADS, LR_P4_THREADS / 256) void lr_persist
             reinterpret_cast<double2*>(tabd), lane, LR_TAB_UNIT, a_lds.cfg.frac_birth, a_lds.cfg.frac_death, ES, nullptr);
         LR_WAVE_LDS_ORDER();
         lr_pair_planes_wave(tabd, H, a_lds.cfg.n_bins, lane, 0);
-        if (lane == 0) {
-            if (SPEC) pend[2 * ch + par].sc[LR_S_CONST_P] = constP;
-            else st_f64[ch][LR_ROW_SCALARS * LR_ROW + LR_S_CONST_P] = constP;
-        }
-        column_stands();
+        if (lane == 0) st_f64[ch][LR_ROW_SCALARS * LR_ROW + LR_S_CONST_P] = constP;
     };
     if (tid == 0) arrived = 0;
-    if (tid < (SPEC ? 8 : 2)) hands[tid].epoch = 0;
+    if (tid < 2) hands[tid].epoch = 0;
     for (int i = tid; i < 2 * NW * 2; i += LR_P4_THREADS) (&red[0][0][0])[i] = 0.0;
     int scans_done = 0;
     // a scanning wave's end of scan number `scans_done` for pair `pr` (HELP: the helper waves score a share too - slots NS,
@@ -749,7 +596,7 @@ __global__ __launch_bounds__(LR_P4_THREADS, LR_P4_THREADS / 256) void lr_persist
         if (LAST_SUMS) {
             lr_p4_leave_sums<NA>(part, &arrived, &red[pr][2][0], wave >= W0 ? wave - W0 : NS + wave - 2, lane, scans_done, s0, s1);
         } else {
-            // (-DLR_P4_LAST_SUMS=0: every scanning wave adds its own lanes up; the stepper adds the waves' sums in wave order)
+            // (general times: every scanning wave adds its own lanes up; the stepper adds the waves' sums in wave order)
             s0 = lr_wave_sum(s0), s1 = lr_wave_sum(s1);
             if (lane == 0) red[pr][wave][0] = s0, red[pr][wave][1] = s1;
         }
@@ -762,8 +609,6 @@ __global__ __launch_bounds__(LR_P4_THREADS, LR_P4_THREADS / 256) void lr_persist
         const int* I = a.state_i32 + (size_t)c * LR_ISTATE_ROWS * LR_ROW;
         for (int r = 0; r < LR_STATE_ROWS; ++r) st_f64[wave][r * LR_ROW + lane] = S[r * LR_ROW + lane];
         for (int r = 0; r < LR_ISTATE_ROWS; ++r) st_i32[wave][r * LR_ROW + lane] = I[r * LR_ROW + lane];
-        // SPEC: the pending proposal into the slot of its iteration's parity (the rows keep the accepted side)
-        if (SPEC) lr_pend_from_rows(S, I, &pend[2 * wave + (I[LR_IROW_SCALARS * LR_ROW + LR_I_IT_LO] & 1)], lane);
     }
     double2* g0 = lr_chain_table(a, c0);
     double2* g1 = lr_chain_table(a, c0 + 2);             // tables are allocated for whole groups of cb >= 4 chains
@@ -785,15 +630,6 @@ __global__ __launch_bounds__(LR_P4_THREADS, LR_P4_THREADS / 256) void lr_persist
     const bool scanner = wave >= W0;
     const bool helper = HELP && (wave == 2 || wave == 3);
     const int sid = tid - W0 * LR_WAVE;
-#if LR_P4_AGE_PRIO
-    // (experiment) issue priorities that offset the arbiter's oldest-first rule among the scanners of a SIMD: waves 4..7
-    // priority 0, 8..11 1, 12..15 2, steppers and helpers 3 - in the step-less kernel the youngest scanners end their scans
-    // 0.6 us after the oldest, and a phase waits for them
-    if (!scanner) __builtin_amdgcn_s_setprio(3);
-    else if (wave >= 12) __builtin_amdgcn_s_setprio(LR_P4_AGE_PRIO == 2 ? 1 : 2);
-    else if (wave >= 8) __builtin_amdgcn_s_setprio(LR_P4_AGE_PRIO == 2 ? 0 : 1);
-    else __builtin_amdgcn_s_setprio(0);
-#endif
     // The SIMD issue arbiter serves its oldest wave first: with equal shares the scanner waves of a SIMD finish one
     // after the other (5.0 / 6.4 / 7.9 / 9.5 us per phase, measured with in-kernel stamps), the youngest runs the tail
     // alone, and SIMDs 0, 1 carry the stepper waves on top.  So the waves get unequal shares (lr_p4_shares) chosen to
@@ -823,119 +659,21 @@ __global__ __launch_bounds__(LR_P4_THREADS, LR_P4_THREADS / 256) void lr_persist
     static_assert(2 * NW * 8 + 4 <= LR_P4_CARRY_BYTES, "");
     char* carry = carry_all ? carry_all + (size_t)blockIdx.x * LR_P4_CARRY_BYTES : nullptr;
     const bool carried = carry && *reinterpret_cast<const int*>(carry + 2 * NW * 8) == 1;
-    // (SPEC: the first stepper phases need the draws of the iterations 1 and 2 beyond the pending one for pair 0, and of
-    // iteration 1 for pair 1 (phase A's scan of pair 1 adds its iteration 2): three pairs of scanner waves, a call each)
-    auto prologue_draws = [&]() {
-        if (SPEC) draw_duty(0, 1, 2), draw_duty(0, 2, 6), draw_duty(1, 1, 10);     // (waves 6, 7; 10, 11; 14, 15: SIMDs 2, 3)
-        else if (HELP && LR_P4_STEPPER_DRAWS) draw_duty(0, 1, 0), draw_duty(1, 1, 2);    // both pairs' first steps; later ones: the steppers
-        else draw_duty(0);
-    };
+    auto prologue_draws = [&]() { draw_duty(0); };      // the draws of the first phase's steps
     if (carried) {
         if (tid < 2 * NW) (&red[0][0][0])[tid] = reinterpret_cast<const double*>(carry)[tid];
         if (scanner) prologue_draws();
     } else if (scanner) {
         double s0 = 0.0, s1 = 0.0;
         lr_scan_tail tail;
-        lr_persist_scan<H, GENERAL, GENERAL ? 1 : LR_P4_UNROLL, false, true>(reinterpret_cast<const char*>(tab[0]), pk, nh, n8w, sid, LR_P4_SCANNERS, &s0, &s1, nullptr, &tail);
-        if (LAST_SUMS) {
-            leave_sums(0, s0, s1);
-        } else {
-            s0 = lr_wave_sum(s0), s1 = lr_wave_sum(s1);
-            if (lane == 0) red[0][wave][0] = s0, red[0][wave][1] = s1;
-        }
+        lr_persist_scan<H, GENERAL, 1, false, true>(reinterpret_cast<const char*>(tab[0]), pk, nh, n8w, sid, LR_P4_SCANNERS, &s0, &s1, nullptr, &tail);
+        leave_sums(0, s0, s1);
         lr_scan_drain(tail);
         prologue_draws();
     }
     if (helper && !carried) help_scan(0);
-    // (SPEC: parity of the pending iteration of this helper's two chains at the start of the launch)
-    int it0_par0 = 0, it0_par1 = 0;
-    if (SPEC && helper) {
-        it0_par0 = st_i32[wave - 2][LR_IROW_SCALARS * LR_ROW + LR_I_IT_LO] & 1;
-        it0_par1 = st_i32[2 + wave - 2][LR_IROW_SCALARS * LR_ROW + LR_I_IT_LO] & 1;
-    }
     __syncthreads();
     LR_PSTAMP(3);      // prologue done: pair 0's sums (scanned or carried), the first draws
-    if (FLOW) {
-        // ---- the phases without their barrier (see lr_p4_flow_lds) ----
-        // pair 0's proposal 0 is scored (prologue / carried), both pairs' tables of proposal 0 stand
-        static_assert(!FLOW || NA == 14, "lr_p4_flow_lds holds fourteen scanning waves' sums per pair");
-        if (tid == 0) {
-            fl->arrived[0] = NA, fl->arrived[1] = 0, fl->sums_epoch[0] = 1, fl->sums_epoch[1] = 0;
-            fl->tab_epoch[0] = 2, fl->tab_epoch[1] = 2, fl->abort = 0;
-        }
-        // the pending iterations of the two chains a drawing wave serves (scanner slots 0, 1: chain k of either pair)
-        unsigned long long itd0 = 0, itd1 = 0;
-        constexpr int DQ = SPEC ? LR_P4_DRAW_WAVE : 0;          // first of the two scanner slots that draw
-        const bool drawer = scanner && wave - W0 >= DQ && wave - W0 < DQ + 2;
-        if (drawer) {
-            const int* I0 = st_i32[wave - W0 - DQ] + LR_IROW_SCALARS * LR_ROW;
-            const int* I1 = st_i32[2 + wave - W0 - DQ] + LR_IROW_SCALARS * LR_ROW;
-            itd0 = (unsigned long long)(unsigned int)I0[LR_I_IT_HI] << 32 | (unsigned int)I0[LR_I_IT_LO];
-            itd1 = (unsigned long long)(unsigned int)I1[LR_I_IT_HI] << 32 | (unsigned int)I1[LR_I_IT_LO];
-        }
-        __syncthreads();
-        // end of a wave's share of scan `q` of pair `pr`: its lanes' sums, its count - and the sums of the block by the wave
-        // that arrives last (per lane over the slots in slot order, then across the lanes: the same order whoever it is)
-        auto leave_flow = [&](int pr, int q, double s0, double s1) {
-            const int slot = wave >= W0 ? wave - W0 : NS + wave - 2;
-            fl->part[pr][slot][lane] = make_double2(s0, s1);
-            int prev = 0;
-            if (lane == 0) prev = __hip_atomic_fetch_add(&fl->arrived[pr], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            prev = __builtin_amdgcn_readfirstlane(prev);
-            if (prev == NA * (q + 1) - 1) {
-                asm volatile("" ::: "memory");
-                double a0 = 0.0, a1 = 0.0;
-#pragma unroll
-                for (int w = 0; w < NA; ++w) {
-                    const double2 v = fl->part[pr][w][lane];
-                    a0 += v.x, a1 += v.y;
-                }
-                a0 = lr_wave_sum(a0), a1 = lr_wave_sum(a1);
-                if (lane == 0) red[pr][2][0] = a0, red[pr][2][1] = a1;
-                LR_WAVE_LDS_ORDER();
-                if (lane == 0) __hip_atomic_store(&fl->sums_epoch[pr], q + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            }
-        };
-        if (helper) {
-            for (long long iter = 0; iter < n_iters; ++iter) {
-#pragma unroll 1
-                for (int ph = 0; ph < 2; ++ph) {
-                    const int pr = 1 - ph, q = (int)iter + ph;          // pair 1's scan `iter`, then pair 0's scan `iter + 1`
-                    if (!lr_flow_wait(&fl->tab_epoch[pr], 2 * (q + 1), &fl->abort)) goto flow_done;
-                    double s0 = 0.0, s1 = 0.0;
-                    if (nh > 0) lr_persist_scan<H, GENERAL, 1, false, false>(reinterpret_cast<const char*>(tab[pr]), pk, 0, nh, tid - 2 * LR_WAVE, 2 * LR_WAVE, &s0, &s1);
-                    leave_flow(pr, q, s0, s1);
-                    help_duty(ph, (int)((2 * iter + ph + 1) & 0x3fffffff), SPEC ? ((ph ? it0_par1 : it0_par0) + (int)(iter & 1) + 1) & 1 : 0);
-                    if (__hip_atomic_load(&fl->abort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) goto flow_done;
-                }
-            }
-        } else if (!scanner) {
-            lr_persist4_steppers<(H <= 264 ? lr_bins_per_lane(H) : 0), ES, NW, PARAM ? 1 : 0, HELP, SPEC, true>(
-                (const __attribute__((address_space(3))) lr_step_args*)&a_lds, c0, C, wave, lane,
-                (__attribute__((address_space(3))) lr_seg_scratch*)&scratch[SPEC ? 0 : wave], (lr_lds_f64*)&st_f64[0][0], (lr_lds_i32*)&st_i32[0][0],
-                (lr_lds_f64*)&red[0][0][0], (lr_lds_f64*)reinterpret_cast<double*>(tab[0]), 2 * LR_UNIT_PLANES * H,
-                (lr_lds_f64*)&br_lds[0][0], n_iters, &draws[0], &hands[0], &pend[0], fl);
-        } else {
-            for (long long iter = 0; iter < n_iters; ++iter) {
-#pragma unroll
-                for (int ph = 0; ph < 2; ++ph) {
-                    const int pr = 1 - ph, q = (int)iter + ph;
-                    if (!lr_flow_wait(&fl->tab_epoch[pr], 2 * (q + 1), &fl->abort)) goto flow_done;
-                    double s0 = 0.0, s1 = 0.0;
-                    lr_scan_tail tail;
-                    lr_persist_scan<H, GENERAL, LR_P4_UNROLL, false, true>(reinterpret_cast<const char*>(tab[pr]), pk, nh, n8w, sid, LR_P4_SCANNERS, &s0, &s1, nullptr, &tail);
-                    // the draws of the step that follows this scan BEFORE this wave counts as arrived (the stepper starts on the count)
-                    // (SPEC: two iterations beyond the proposal just scored - what the stepper stages at this decision)
-                    if (drawer) draw_duty(pr, SPEC ? 2 : 1, DQ, (pr ? itd1 : itd0) + (unsigned long long)q + (SPEC ? 2ull : 1ull));
-                    leave_flow(pr, q, s0, s1);
-                    lr_scan_drain(tail);
-                }
-            }
-        }
-    flow_done:
-        __syncthreads();
-        if (tid == 0 && fl->abort) __hip_atomic_store(ap->warn - 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // status: a wait timed out
-    } else
     // phase ph of an iteration: the steppers advance pair `ph`, the scanners score pair `1 - ph`
     if (helper) {
         for (long long iter = 0; iter < n_iters; ++iter) {
@@ -945,7 +683,7 @@ __global__ __launch_bounds__(LR_P4_THREADS, LR_P4_THREADS / 256) void lr_persist
                 const unsigned long long dq0 = wall_clock64();
 #endif
                 help_scan(1 - ph);
-                help_duty(ph, (int)((2 * iter + ph + 1) & 0x3fffffff), SPEC ? ((ph ? it0_par1 : it0_par0) + (int)(iter & 1) + 1) & 1 : 0);
+                help_duty(ph, (int)((2 * iter + ph + 1) & 0x3fffffff));
 #ifdef LR_DIAG
                 const unsigned long long dq1 = wall_clock64();
 #endif
@@ -959,11 +697,11 @@ __global__ __launch_bounds__(LR_P4_THREADS, LR_P4_THREADS / 256) void lr_persist
             }
         }
     } else if (!scanner)
-        lr_persist4_steppers<(H <= 264 ? lr_bins_per_lane(H) : 0), ES, NW, PARAM ? 1 : 0, HELP, SPEC>(
+        lr_persist4_steppers<(H <= 264 ? lr_bins_per_lane(H) : 0), ES, NW, PARAM ? 1 : 0, HELP>(
             (const __attribute__((address_space(3))) lr_step_args*)&a_lds, c0, C, wave, lane,
-            (__attribute__((address_space(3))) lr_seg_scratch*)&scratch[SPEC ? 0 : wave], (lr_lds_f64*)&st_f64[0][0], (lr_lds_i32*)&st_i32[0][0],
+            (__attribute__((address_space(3))) lr_seg_scratch*)&scratch[wave], (lr_lds_f64*)&st_f64[0][0], (lr_lds_i32*)&st_i32[0][0],
             (lr_lds_f64*)&red[0][0][0], (lr_lds_f64*)reinterpret_cast<double*>(tab[0]), 2 * LR_UNIT_PLANES * H,
-            (lr_lds_f64*)&br_lds[0][0], n_iters, &draws[0], &hands[0], &pend[0]);
+            (lr_lds_f64*)&br_lds[0][0], n_iters, &draws[0], &hands[0]);
     else
     for (long long iter = 0; iter < n_iters; ++iter) {
 #pragma unroll
@@ -974,15 +712,10 @@ __global__ __launch_bounds__(LR_P4_THREADS, LR_P4_THREADS / 256) void lr_persist
             {
                 double s0 = 0.0, s1 = 0.0;
                 lr_scan_tail tail;
-                lr_persist_scan<H, GENERAL, GENERAL ? 1 : LR_P4_UNROLL, false, true>(reinterpret_cast<const char*>(tab[1 - ph]), pk, nh, n8w, sid, LR_P4_SCANNERS, &s0, &s1, nullptr, &tail);
-                if (LAST_SUMS) {
-                    leave_sums(1 - ph, s0, s1);
-                } else {
-                    s0 = lr_wave_sum(s0), s1 = lr_wave_sum(s1);
-                    if (lane == 0) red[1 - ph][wave][0] = s0, red[1 - ph][wave][1] = s1;
-                }
+                lr_persist_scan<H, GENERAL, 1, false, true>(reinterpret_cast<const char*>(tab[1 - ph]), pk, nh, n8w, sid, LR_P4_SCANNERS, &s0, &s1, nullptr, &tail);
+                leave_sums(1 - ph, s0, s1);
                 lr_scan_drain(tail);      // the idle prefetch of the scan's last trip (lr_scan.h)
-                if (!(HELP && !SPEC && LR_P4_STEPPER_DRAWS)) draw_duty(1 - ph);
+                draw_duty(1 - ph);
             }
 #ifdef LR_DIAG
             const unsigned long long dq1 = wall_clock64();
@@ -1001,10 +734,6 @@ __global__ __launch_bounds__(LR_P4_THREADS, LR_P4_THREADS / 256) void lr_persist
         const int c = c0 + wave;
         double* S = a.state_f64 + (size_t)c * LR_STATE_ROWS * LR_ROW;
         int* I = a.state_i32 + (size_t)c * LR_ISTATE_ROWS * LR_ROW;
-        if (SPEC) {      // the pending proposal back into the rows (the staged candidate is dropped: the next launch re-proposes)
-            lr_pend_to_rows(st_f64[wave], st_i32[wave], &pend[2 * wave + (st_i32[wave][LR_IROW_SCALARS * LR_ROW + LR_I_IT_LO] & 1)], lane);
-            LR_WAVE_LDS_ORDER();
-        }
         for (int r = 0; r < LR_STATE_ROWS; ++r) S[r * LR_ROW + lane] = st_f64[wave][r * LR_ROW + lane];
         for (int r = 0; r < LR_ISTATE_ROWS; ++r) I[r * LR_ROW + lane] = st_i32[wave][r * LR_ROW + lane];
     }
@@ -1576,7 +1305,6 @@ extern "C" int lr_mcmc_create(const lr_mcmc_config* cfg, const double* ts, const
     for (int j = 0; j < 16; ++j) e->p4.delta[j] = 0;
     e->p4.n_slots = 8;
     e->p4_help = lr_p4_help_choice(e);                  // (lr_mcmc_describe before init; latched again by lr_set_shares)
-    e->p4_spec = lr_p4_spec_choice(e);
     e->streaming = false;
     e->packed_scan = lay.packed_scan != 0;
     e->fork = nullptr;
@@ -1917,9 +1645,7 @@ extern "C" int lr_mcmc_steps(lr_engine* e, int64_t n_iters, void* stream_) {
         const bool param = e->cfg.sampler != 0;
         static const int prio = lr_env_int("LR_PERSIST_PRIO", 12);   // clock bits per priority slice, 0 = off
         // one block per CU at most: give it the whole CU (16 waves on the one pair)
-        static const int wide_env = lr_env_int("LR_PERSIST_WIDE", -1);
         const bool wide = e->lay.reserved1 == 1024;   // (short scans keep 512: the 16-wave barrier costs more than it buys)
-        (void)wide_env;
         if (e->lay.persistent == 3) return lr_launch_spec(e, a, pk, n_iters, stream);
         for (int64_t done = 0; done < n_iters;) {
             const int64_t n = (n_iters - done > 4096) ? 4096 : n_iters - done;   // keep single launches short
@@ -1931,22 +1657,8 @@ extern "C" int lr_mcmc_steps(lr_engine* e, int64_t n_iters, void* stream_) {
         if (general && param) hipLaunchKernelGGL((lr_persist4_kernel<HH, true, true>), g4, b4, 0, stream, ap, pk, e->n8, e->p4, (long long)n, p4_carry);   \
         else if (general) hipLaunchKernelGGL((lr_persist4_kernel<HH, true, false>), g4, b4, 0, stream, ap, pk, e->n8, e->p4, (long long)n, p4_carry);      \
         else if (param) hipLaunchKernelGGL((lr_persist4_kernel<HH, false, true>), g4, b4, 0, stream, ap, pk, e->n8, e->p4, (long long)n, p4_carry);        \
-        else if (e->p4_help && e->p4_spec) {                                                                                   \
-            /* (helper waves: H <= 264, lr_p4_help_choice; the attribute belongs to the function on the CURRENT device) */     \
-            const size_t dyn_ = LR_P4_FLOW ? LR_P4_SPEC_LDS_BYTES + sizeof(lr_p4_flow_lds) : sizeof(lr_p4_spec_lds);            \
-            hipError_t he_ = hipFuncSetAttribute(reinterpret_cast<const void*>(&lr_persist4_kernel<(HH <= 264 ? HH : 264), false, false, true, true>), \
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn_);                       \
-            if (he_ != hipSuccess) return (int)he_;                                                                            \
-            hipLaunchKernelGGL((lr_persist4_kernel<(HH <= 264 ? HH : 264), false, false, true, true>), g4, b4, dyn_, stream, ap, pk, e->n8, e->p4, (long long)n, p4_carry); \
-        }                                                                                                                      \
-        else if (e->p4_help) {                                                                                                 \
-            if (LR_P4_FLOW) {                                                                                                  \
-                hipError_t he_ = hipFuncSetAttribute(reinterpret_cast<const void*>(&lr_persist4_kernel<(HH <= 264 ? HH : 264), false, false, true>), \
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(lr_p4_flow_lds)); \
-                if (he_ != hipSuccess) return (int)he_;                                                                        \
-            }                                                                                                                  \
-            hipLaunchKernelGGL((lr_persist4_kernel<(HH <= 264 ? HH : 264), false, false, true>), g4, b4, LR_P4_FLOW ? sizeof(lr_p4_flow_lds) : 0, stream, ap, pk, e->n8, e->p4, (long long)n, p4_carry); \
-        }                                                                                                                      \
+        else if (e->p4_help)      /* (helper waves: H <= 264, lr_p4_help_choice) */                                           \
+            hipLaunchKernelGGL((lr_persist4_kernel<(HH <= 264 ? HH : 264), false, false, true>), g4, b4, 0, stream, ap, pk, e->n8, e->p4, (long long)n, p4_carry); \
         else hipLaunchKernelGGL((lr_persist4_kernel<HH, false, false>), g4, b4, 0, stream, ap, pk, e->n8, e->p4, (long long)n, p4_carry);                  \
     } else if (wide) {                                                                                                        \
         hipLaunchKernelGGL((lr_persist_kernel<HH, 1024>), dim3(blocks), dim3(1024), 0, stream, ap, idx8, e->n8, e->p4, (long long)n, 0); \
@@ -2043,8 +1755,8 @@ extern "C" int lr_mcmc_describe(const lr_engine* e, char* buf, int32_t n) {
             snprintf(buf, (size_t)n, "lr_spec_kernel<%d, %d, %s, %s, %d>", e->plan.H, e->lay.reserved1, e->cfg.sampler == 0 ? "true" : "false", gen,
                      lr_spec_mode(e));
         else if (e->lay.persistent == 2)
-            snprintf(buf, (size_t)n, "lr_persist4_kernel<%d, %s, %s, %s, %s>", e->plan.H, gen, e->cfg.sampler != 0 ? "true" : "false",
-                     e->p4_help ? "true" : "false", (e->p4_help && e->p4_spec) ? "true" : "false");
+            snprintf(buf, (size_t)n, "lr_persist4_kernel<%d, %s, %s, %s>", e->plan.H, gen, e->cfg.sampler != 0 ? "true" : "false",
+                     e->p4_help ? "true" : "false");
         else snprintf(buf, (size_t)n, "lr_persist_kernel<%d, %d>", e->plan.H, e->lay.reserved1);
     } else if (e->packed_scan) {
         snprintf(buf, (size_t)n, "lr_packscan_kernel<%d, %d, %s>", lr_packscan_pairs(e->plan, e->cfg.n_chains), e->plan.H,

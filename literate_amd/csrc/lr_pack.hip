@@ -214,7 +214,6 @@ static void lr_set_shares(lr_engine* e) {
     for (int j = 0; j < 16; ++j) e->p4.delta[j] = 0;
     e->p4.help_trips = 0;
     e->p4_help = lr_p4_help_choice(e);
-    e->p4_spec = lr_p4_spec_choice(e);
     if (e->lay.persistent == 2 && e->p4_help) {
         // a helper wave is idle until its stepper's hand-over arrives (~1.2 us into a phase, a scan trip takes ~0.3 us):
         // it scores the first groups meanwhile (the 128 helper lanes stride over [0, 128 trips), the scanners over the rest).
@@ -237,16 +236,12 @@ static void lr_set_shares(lr_engine* e) {
         // equal; the knob stays for experiments)
         int base[7] = {0, 0, 0, 0, 0, 0, 0};
         if (env && e->p4.n_slots == 14) sscanf(env, "%d,%d,%d,%d,%d,%d,%d", &base[0], &base[1], &base[2], &base[3], &base[4], &base[5], &base[6]);
-        // helper form: "d4,d6,d8,d10,d12,d14" per wave pair (4,5) ... (14,15), trips per 9 trips of a scanner lane
-        // (SIMDs 0, 1 - pairs (4,5), (8,9), (12,13) - also carry the steppers, SIMDs 2, 3 the helpers)
-        static const char* env12 = getenv("LR_P4_SHARES12");
-        if (env12 && e->p4.n_slots == 12) sscanf(env12, "%d,%d,%d,%d,%d,%d", &base[0], &base[1], &base[2], &base[3], &base[4], &base[5]);
         const long long behind = e->p4_help ? (long long)e->p4.help_trips * 128 : 0;
         const int per = e->p4.n_slots * 64;
         const int k_tot = (int)((e->n8 - behind + per - 1) / per);
         int sum = 0;
         for (int j = 0; j < 7; ++j) {
-            int d = (k_tot >= 6) ? (int)lrint((double)base[j] * k_tot / (e->p4.n_slots == 12 ? 9.0 : 14.0)) : 0;
+            int d = (k_tot >= 6) ? (int)lrint((double)base[j] * k_tot / 14.0) : 0;
             if (d < -(k_tot - 1)) d = -(k_tot - 1);
             if (d > LR_P4_MAX_GIVE) d = LR_P4_MAX_GIVE;
             e->p4.delta[2 * j] = e->p4.delta[2 * j + 1] = d;

@@ -49,18 +49,16 @@ def _oracle_run(G, name, model, seed, chain, n_it, **kw):
                                        (0, dict(engine="spec", team=1, cpt=1, planes_by_scanners=0)),
                                        # (the four-chain kernel's form without helper waves: fourteen scanner waves)
                                        (0, dict(engine="persistent4", p4_help=0)), (3, dict(engine="persistent4", p4_help=0)),
-                                       # (... and its form whose steppers speculate on rejection, LR_P4_SPEC=1: lr_chain_step_respec)
-                                       (0, dict(engine="persistent4", p4_spec=1)), (3, dict(engine="persistent4", p4_spec=1)),
-                                       (2, dict(engine="persistent4", p4_spec=1, const_death_rate=1)),
                                        # (the resident streaming kernel - the planner's choice for few chains x very many
                                        # lineages - forced on this short input: lr_stream.hip)
+                                       (1, dict(engine="stream", unit_resolution=False)), (2, dict(engine="stream", use_rate_HP=0, Poisson_HP=2.5)),
+                                       # (a chain on its own CU with the pair planes by the helper waves, on general times)
+                                       (1, dict(engine="spec", team=1, cpt=1, planes_by_scanners=0, unit_resolution=False)),
                                        # (the launch-based engine scanning the PACKED lineages - the planner's choice for very
                                        # many lineages at unit resolution - forced on this short input: lr_packscan.hip)
                                        (0, dict(engine="packed")), (2, dict(engine="packed", const_rates=1)), (1, dict(engine="packed")),
                                        (3, dict(engine="packed")), (3, dict(engine="packed", unit_resolution=False)),
-                                       (0, dict(engine="stream")), (2, dict(engine="stream", const_rates=1)),
-                                       (1, dict(engine="stream", unit_resolution=False)), (2, dict(engine="stream", use_rate_HP=0, Poisson_HP=2.5)),
-                                       (1, dict(engine="spec", team=1, cpt=1, planes_by_scanners=0, unit_resolution=False))])
+                                       (0, dict(engine="stream")), (2, dict(engine="stream", const_rates=1))])
 def test_engine_follows_oracle_trajectory(G, model, kw, monkeypatch):
     from literate_amd.engine import ChainEngine, split_trace_row
     name, seed, n_it, C, off = "example_TBP", 2024, 1500, 6, 40
@@ -69,8 +67,6 @@ def test_engine_follows_oracle_trajectory(G, model, kw, monkeypatch):
         monkeypatch.setenv("LR_SPEC_PLANES_BY_SCANNERS", str(kw.pop("planes_by_scanners")))
     if "p4_help" in kw:
         monkeypatch.setenv("LR_P4_HELP", str(kw.pop("p4_help")))
-    p4_spec = kw.pop("p4_spec", 0)
-    monkeypatch.setenv("LR_P4_SPEC", str(p4_spec))
     ekw = dict(const_rates=kw.get("const_rates", 0), const_death_rate=kw.get("const_death_rate", 0),
                use_rate_HP=kw.get("use_rate_HP", 1), poisson_HP=kw.get("Poisson_HP", 0.0),
                unit_resolution=kw.pop("unit_resolution", None), engine=kw.pop("engine", "auto"), team=kw.pop("team", 0),
@@ -90,7 +86,8 @@ def test_engine_follows_oracle_trajectory(G, model, kw, monkeypatch):
         assert eng.layout.persistent == 0 and eng.layout.packed_scan == 1 and eng.kernel_name().startswith("lr_packscan_kernel<4,")
         assert eng.kernel_name().endswith("true>" if ekw["unit_resolution"] is False else "false>")
     if ekw["engine"] == "persistent4" and ekw["unit_resolution"] is not False:
-        assert eng.kernel_name().endswith("false, false>" if "LR_P4_HELP" in os.environ else ("true, true>" if p4_spec else "true, false>"))
+        # <H, general, parametric, helper waves>
+        assert eng.kernel_name().endswith("false, false, false>" if "LR_P4_HELP" in os.environ else "false, false, true>")
     # binning done by the engine's own kernel must equal the reference's
     assert np.array_equal(eng.sp_events.cpu().numpy(), G[name + "/sp"])
     assert np.array_equal(eng.br_length.cpu().numpy(), G[name + "/br"])
@@ -685,8 +682,8 @@ def test_checkpoints_append_their_trace_rows_and_can_be_written_behind_the_next_
         e.close()
 
 
-@pytest.mark.parametrize("general", [False, True, "respec"])
-def test_four_chain_kernel_does_not_depend_on_how_a_run_is_cut_into_launches(general, monkeypatch):
+@pytest.mark.parametrize("general", [False, True])
+def test_four_chain_kernel_does_not_depend_on_how_a_run_is_cut_into_launches(general):
     """The four-chain kernel leaves the scan sums of its last phase for the next launch instead of scoring pair 0 again: a
     run cut into launches of 7 + 1 + 32 iterations equals one launch of 40 bit for bit (60k lineages: several trips per
     scanner lane, the helper waves' share included), and a second init() of the same engine - which sets the state
@@ -695,10 +692,6 @@ def test_four_chain_kernel_does_not_depend_on_how_a_run_is_cut_into_launches(gen
     from literate_amd import synth
     from literate_amd.engine import ChainEngine
     ts, te, _ = synth.make_lineages(60_000, n_bins=128, n_shifts=20, seed=11)
-    # "respec": the form whose steppers speculate on rejection drops its staged candidates at every launch boundary and
-    # re-proposes - the same doubles (LR_P4_SPEC is read at init)
-    monkeypatch.setenv("LR_P4_SPEC", "1" if general == "respec" else "0")
-    respec, general = general == "respec", general is True
     if general:
         rng = np.random.default_rng(3)
         ts = ts + rng.uniform(0, 0.999, len(ts))
@@ -710,7 +703,7 @@ def test_four_chain_kernel_does_not_depend_on_how_a_run_is_cut_into_launches(gen
     cut.init(); cut.steps(13)                 # a run whose sums must not leak into the next one
     cut.init(); cut.steps(7); cut.steps(1); cut.steps(32)
     torch.cuda.synchronize()
-    assert one.layout.persistent == 2 and one.kernel_name().endswith("false, false>" if general else ("true, true>" if respec else "true, false>"))
+    assert one.layout.persistent == 2 and one.kernel_name().endswith("true, false, false>" if general else "false, false, true>")
     bits = lambda t: t.contiguous().view(torch.int64)
     assert torch.equal(bits(cut.trace), bits(one.trace))
     assert torch.equal(bits(cut.state_f64), bits(one.state_f64)) and torch.equal(cut.state_i32, one.state_i32)
