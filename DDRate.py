@@ -26,6 +26,9 @@ def build_parser():
                    default=2, metavar=2)
     p.add_argument('-fix_death', type=float, help='Fix death rate (with -m_death -1)', default=0.1, metavar=0.1)
     p.add_argument('--chains', type=int, default=1, help='total number of independent chains (extension)')
+    p.add_argument('--ess', type=float, default=-1.0, help='after the run, write <stem>_ESS.tsv and <stem>_ESS_chains.tsv '
+                   '(per-chain effective sample sizes and split R-hat of the logged parameters, this burn-in fraction '
+                   'dropped per chain) beside the logs; computed on the GPU (extension)')
     p.add_argument('--block', type=int, default=0, help='iterations per device window (logs are flushed once per window; '
                    'default: -p rounded up to ~50000)')
     return p
@@ -33,6 +36,11 @@ def build_parser():
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
+    if args.ess != -1.0:
+        from literate_amd.logs import ess_arg_error
+        err = ess_arg_error(args.ess, args.n, args.s)
+        if err:
+            raise SystemExit(err)
     import torch
     import torch.distributed as dist
     from literate_amd import dist as lrd
@@ -95,6 +103,9 @@ def main(argv=None):
     if rank == 0 and args.n > 0:
         el = time.time() - t_start
         print("%d iterations x %d chains in %.2f s (%.0f iterations/s/chain)" % (args.n, args.chains, el, args.n / el))
+    if args.ess != -1.0:
+        from literate_amd.logs import write_run_ess
+        write_run_ess(eng, n_local, args.chains, world, rank, args.ess, args.s, stem)
     eng.close()
     if world > 1:
         dist.barrier()

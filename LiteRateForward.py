@@ -52,6 +52,10 @@ def build_parser():
                    'of the birth, death and net rates and the frequency of rate shifts per unit bin) and <stem>_RTT_K.tsv '
                    '(histogram of the number of rates) next to the logs, pooled over all chains with this burn-in fraction '
                    'dropped per chain (plotRJforward.v3.py -combine 1); computed on the GPU')
+    p.add_argument('--ess', type=float, default=-1.0, help='after the run, write <stem>_ESS.tsv (per log column: pooled '
+                   'mean and effective sample size, the lowest chain ESS, split R-hat) and <stem>_ESS_chains.tsv (ESS, '
+                   'autocorrelation time and SE of the mean per chain and column) next to the logs, with this burn-in '
+                   'fraction dropped per chain (what the tutorial checks in Tracer); computed on the GPU')
     p.add_argument('--init_shifts', type=int, default=0, help='initial number of rate shifts per process')
     p.add_argument('--block', type=int, default=0, help='iterations per device window: logs are written and flushed and '
                    'the state is printed once per window, while the next one runs (default: -p rounded up to ~50000)')
@@ -93,6 +97,11 @@ def main(argv=None):
                          "does not bin the same way: not supported together")
     if args.rtt >= 1:
         raise SystemExit("--rtt takes a burn-in fraction in [0, 1)")
+    if args.ess != -1.0:
+        from literate_amd.logs import ess_arg_error
+        err = ess_arg_error(args.ess, args.n, args.s)
+        if err:
+            raise SystemExit(err)
     print("\n\n             LiteRate - 20200206 (MI355X engine)\n")
     import torch
     import torch.distributed as dist
@@ -212,6 +221,9 @@ def main(argv=None):
         logs.combine_logs(files, os.path.dirname(files[0]), args.combine)
     if args.rtt >= 0 and n_samples:
         write_rtt(args, eng, n_local, world, rank)
+    if args.ess != -1.0:
+        stem = logs.log_paths(args.d, args.model_BDI, args.out)[1]["div"][:-len("_div.log")]
+        logs.write_run_ess(eng, n_local, args.chains, world, rank, args.ess, args.s, stem)
     eng.close()
     if world > 1:
         dist.destroy_process_group()

@@ -201,6 +201,33 @@ int lr_rtt_summary(const double* trace, int32_t n_samples, int32_t n_chains, dou
                    double burnin, int32_t pooled, double* rates, double* shift_freq, int64_t* k_counts,
                    void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- Convergence summary: per-chain ESS and split R-hat (the check the reference's tutorial does in Tracer) ------------
+ * rows: [n_samples, n_chains, row_width] doubles, row (sample s, chain c) at rows + (s * n_chains + c) * row_width - the
+ * engine's trace (its first n_samples slots) or rows a caller assembled.  cols (host): the n_cols column indices to
+ * diagnose.  Every chain drops its first burn = int(burnin * n_samples) rows and keeps n = n_samples - burn.  Needs
+ * n >= 4, 0 <= burnin < 1, n_cols >= 1, every column in [0, row_width), max_lag >= 1 (else LR_ERR_SIZE).
+ * Per chain c and column k, on the kept series x (Tracer's estimator, BEAST TraceCorrelation):
+ *   m = sum x_j / n, d_j = x_j - m;  L = min(n - 1, max_lag);  g_t = sum_{j < n - t} d_j d_{j+t} / (n - t);
+ *   V = g_0, then for t = 2, 4, ... while t < L: V += 2 (g_{t-1} + g_t) while that pair sum is > 0, else stop_lag = t;
+ *   stop_lag = L if the loop runs out.  ACT = V / g_0 (samples), ESS = n / ACT, SE_mean = sqrt(V / n).
+ *   g_0 == 0 (constant after burn-in): mean = the value, SE_mean = 0, stop_lag = 0, ACT = ESS = NaN.
+ *   (A sequence of equal values has that value as its mean, here and for the R-hat halves below.)
+ * Per column: pooled_mean = the mean of the chain means; pooled_ess = the sum of the finite chain ESS (NaN if none);
+ *   rhat = split R-hat (BDA3 11.4): h = n / 2, chain c gives its kept rows [0, h) and [n - h, n); M = 2C sequences of
+ *   means mu_q and variances s2_q (divisor h - 1); B = h / (M - 1) sum (mu_q - mu)^2, W = mean s2_q;
+ *   rhat = sqrt(((h - 1) / h W + B / h) / W), NaN when W == 0.
+ * Outputs: chain_stats [n_cols, n_chains, 4] = (mean, ess, act, se_mean); stop_lag [n_cols, n_chains];
+ *   col_stats [n_cols, 3] = (pooled_mean, pooled_ess, rhat).
+ * Every sum has an order fixed by the shape alone (no floating-point atomics): the same rows give the same bits.  A
+ * series of n <= LR_ESS_LDS_ROWS kept rows is held in LDS; a longer one is centred into the workspace and read from
+ * there.  The size query validates the arguments on the host (no device); a smaller workspace is LR_ERR_WORKSPACE.     */
+#define LR_ESS_LDS_ROWS 16384
+int64_t lr_ess_summary_workspace_bytes(int32_t n_samples, int32_t n_chains, int32_t row_width, const int32_t* cols,
+                                       int32_t n_cols, double burnin, int32_t max_lag);
+int lr_ess_summary(const double* rows, int32_t n_samples, int32_t n_chains, int32_t row_width, const int32_t* cols,
+                   int32_t n_cols, double burnin, int32_t max_lag, double* chain_stats, int32_t* stop_lag,
+                   double* col_stats, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- A11: fused multi-chain RJMCMC --------------------------------------------------------
  * Replaces runMCMC (LRF:216-373) for n_chains independent chains.  Per iteration: one scan of
  * the lineage arrays scoring every chain's proposal, then one chain-step kernel (reduce,

@@ -15,6 +15,7 @@ LR_WARN_KCAP = 2
 LR_STATE_ROWS, LR_ISTATE_ROWS = 9, 5
 LR_TRACE_HEAD = 13
 LR_TRACE_W = LR_TRACE_HEAD + 2 * (2 * LR_KMAX - 1)
+LR_ESS_LDS_ROWS = 16384      # lr_ess_summary: longest kept series held in LDS (longer ones stream from the workspace)
 # rows / scalar slots (include/literate_hip.h)
 ROW_L, ROW_M, ROW_TL, ROW_TM, ROW_PL, ROW_PM, ROW_PTL, ROW_PTM, ROW_SCALARS = range(9)
 (S_LIKA, S_PRIORA, S_PRIORPOIA, S_GRATE_L, S_GRATE_M, S_POI, S_HASTING, S_PRIOR_P, S_PRIORPOI_P, S_CONST_P,
@@ -67,6 +68,8 @@ SIGNATURES = {
     "lr_format_rows": (c_i64, [c_vp, c_vp, c_i64, C.c_uint64, c_i32, c_vp, c_i64]),
     "lr_rtt_summary_workspace_bytes": (c_i64, [c_i32, c_i32, c_f64, c_f64, c_f64, c_i32]),
     "lr_rtt_summary": (c_i32, [c_vp, c_i32, c_i32, c_f64, c_f64, c_f64, c_i32, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "lr_ess_summary_workspace_bytes": (c_i64, [c_i32, c_i32, c_i32, c_vp, c_i32, c_f64, c_i32]),
+    "lr_ess_summary": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_i32, c_f64, c_i32, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
     "lr_mcmc_query_layout": (c_i32, [C.POINTER(McmcConfig), C.POINTER(McmcLayout)]),
     "lr_mcmc_create": (c_i32, [C.POINTER(McmcConfig), c_vp, c_vp, c_vp, c_vp, c_i64, C.POINTER(c_vp)]),
     "lr_mcmc_init": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp]),

@@ -68,6 +68,14 @@ class DDRateEngine(ChainEngine):
                 O[:, 14 + 4 * n:] = logs.adequacy_rows(emp[0], emp[1], b, d)
         return out.reshape(lead + (out.shape[1],))
 
+    def ess_rows(self, rows):
+        """The trace rows' first 12 columns (it, posterior, likelihood, prior, args[8]) with midpoint_x0 and maxCarryingCap
+        formed on the device as log_table_from forms them (x0 + ORIGIN, L + div_0): the values as the log holds them."""
+        out = rows[..., :12].clone()
+        out[..., 6] += self.origin                # DD:224
+        out[..., 8] += out[..., 7]                # DD:225
+        return out, list(range(1, 12)), ["it", "posterior", "likelihood", "prior"] + LOG_HEAD[6:14]
+
     def log_head(self):
         n = len(self.DT)
         head = list(LOG_HEAD)

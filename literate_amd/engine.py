@@ -448,6 +448,25 @@ class ChainEngine:
         return ops.rtt_summary(self.trace, self.samples_done(), self.cfg.start_time, self.cfg.end_time, burnin, pooled,
                                workspace_bytes)
 
+    def ess_rows(self, rows):
+        """Trace rows [S, C, LR_TRACE_W] -> (rows whose columns hold the log's values as the log holds them, the indices of
+        the sampler's diagnosable columns there, the names of the rows' leading columns).  runMCMC logs its trace head
+        as it is: posterior .. K_m and the three hyper-priors (trace columns 1-7, 10-12)."""
+        from .logs import MCMC_HEAD
+        return rows, [1, 2, 3, 4, 5, 6, 7, 10, 11, 12], list(MCMC_HEAD)
+
+    def ess_summary(self, burnin=0.1, columns=None, max_lag=2000):
+        """Convergence summary (ops.ess_summary: per-chain ESS, pooled ESS, split R-hat) of the rows sampled so far, on the
+        resident trace; also after load() of a checkpoint.  columns: indices into ess_rows' rows (default: the
+        sampler's diagnosable log columns).  Returns (EssSummary, column names)."""
+        self.check_status()
+        S = self.samples_done()
+        rows, cols, head = self.ess_rows(self.trace[:S])
+        if columns is not None:
+            cols = [int(c) for c in columns]
+        names = [head[c] if c < len(head) else "col_%d" % c for c in cols]
+        return ops.ess_summary(rows, S, cols, burnin, max_lag), names
+
     def trace_rows(self, n_samples=None):
         """Trace buffer as numpy [samples, chains, LR_TRACE_W] (see include/literate_hip.h)."""
         self.check_status()

@@ -445,3 +445,77 @@ def write_rtt_tables(stem, time, rates, shift_freq, k_counts):
         f.write("n_rates\tK_l\tK_m\n")
         for k in range(k_counts.shape[1]):
             f.write("%d\t%d\t%d\n" % (k + 1, int(k_counts[0, k]), int(k_counts[1, k])))
+
+
+ESS_HEAD = ["parameter", "mean", "ess_pooled", "ess_min", "chain_ess_min", "rhat", "chains_ess_below_200", "chains_constant"]
+ESS_CHAIN_HEAD = ["chain", "parameter", "mean", "ess", "act", "se_mean", "stop_lag"]
+
+
+def ess_arg_error(burnin, n_iterations, s_freq):
+    """Why a CLI's --ess BURNIN cannot run (None when it can): a burn-in fraction outside [0, 1), or fewer than 4 samples
+    per chain after burn-in (ceil(n / s) - int(BURNIN * ceil(n / s)))."""
+    if not (0.0 <= burnin < 1.0):
+        return "--ess takes a burn-in fraction in [0, 1)"
+    S = (n_iterations + s_freq - 1) // s_freq if n_iterations > 0 and s_freq > 0 else 0
+    if S - int(burnin * S) < 4:
+        return "--ess %s keeps %d of the %d samples per chain: the summary needs at least 4" % (burnin, S - int(burnin * S), S)
+    return None
+
+
+def write_ess_tables(stem, names, res, s_freq=1):
+    """<stem>_ESS.tsv (one line per column, ESS_HEAD) and <stem>_ESS_chains.tsv (one line per chain and column,
+    ESS_CHAIN_HEAD) from host arrays of one ops.ess_summary (res: mean, ess, act, se_mean, stop_lag [C, K]; pooled_mean,
+    pooled_ess, rhat [K]).  act is written in iterations (ACT x s_freq), as Tracer reports it.  Numbers as str(float), as
+    the logs write them.  Returns the one-line report the CLIs print."""
+    ess, stop = np.asarray(res.ess, dtype=float), np.asarray(res.stop_lag)
+    C, K = ess.shape
+    fin = np.isfinite(ess)
+    with open(stem + "_ESS.tsv", "w") as f:
+        f.write("\t".join(ESS_HEAD) + "\n")
+        for k in range(K):
+            if fin[:, k].any():
+                c_min = int(np.argmin(np.where(fin[:, k], ess[:, k], np.inf)))     # the lowest chain id on a tie
+                e_min, c_txt = str(float(ess[c_min, k])), "%d" % c_min
+            else:
+                e_min = c_txt = "nan"
+            f.write("\t".join([names[k], str(float(res.pooled_mean[k])), str(float(res.pooled_ess[k])), e_min, c_txt,
+                               str(float(res.rhat[k])), "%d" % int((fin[:, k] & (ess[:, k] < 200)).sum()),
+                               "%d" % int((stop[:, k] == 0).sum())]) + "\n")
+    with open(stem + "_ESS_chains.tsv", "w") as f:
+        f.write("\t".join(ESS_CHAIN_HEAD) + "\n")
+        for c in range(C):
+            for k in range(K):
+                f.write("%d\t%s\t%s\t%s\t%s\t%s\t%d\n" % (c, names[k], str(float(res.mean[c, k])), str(float(ess[c, k])),
+                                                         str(float(res.act[c, k]) * s_freq), str(float(res.se_mean[c, k])),
+                                                         int(stop[c, k])))
+    if fin.any():
+        c, k = np.unravel_index(int(np.argmin(np.where(fin, ess, np.inf).T)), (K, C))[::-1]
+        low = "lowest ESS %s (%s, chain %d)" % (str(float(ess[c, k])), names[k], c)
+    else:
+        low = "lowest ESS nan (no chain has a finite ESS)"
+    rh = np.asarray(res.rhat, dtype=float)
+    if np.isfinite(rh).any():
+        k = int(np.nanargmax(rh))
+        high = "highest R-hat %s (%s)" % (str(float(rh[k])), names[k])
+    else:
+        high = "highest R-hat nan"
+    below = int((fin & (ess < 200)).any(axis=1).sum())
+    return "convergence: %s, %s, %d of %d chains below ESS 200 in some column: %s_ESS.tsv, %s_ESS_chains.tsv" % (
+        low, high, below, C, stem, stem)
+
+
+def write_run_ess(eng, n_local, total_chains, world, rank, burnin, s_freq, stem):
+    """The CLIs' --ess: ops.ess_summary of the sampler's log columns (eng.ess_rows) over the rows the run sampled ->
+    <stem>_ESS.tsv and <stem>_ESS_chains.tsv on rank 0, and the report printed.  The rows are gathered to rank 0's device
+    once, so any number of ranks and a resumed run write the same bytes."""
+    from . import dist as lrd
+    from . import ops
+    S = eng.samples_done()
+    local = eng.trace[:S][:, :n_local]
+    rows = lrd.gather_traces(local.contiguous(), total_chains) if world > 1 else local
+    if rank != 0:
+        return
+    rows, cols, head = eng.ess_rows(rows)
+    res = ops.ess_summary(rows, S, cols, burnin=burnin)
+    host = res._replace(**{k: getattr(res, k).cpu().numpy() for k in res._fields if k != "n"})
+    print(write_ess_tables(stem, [head[c] for c in cols], host, s_freq))

@@ -432,6 +432,42 @@ def rtt_summary(trace, n_samples, start_age, end_age, burnin=0.2, pooled=True, w
     return RttSummary(time, rates, freq, kc, per * C if pooled else per)
 
 
+EssSummary = namedtuple("EssSummary", "mean ess act se_mean stop_lag pooled_mean pooled_ess rhat n")
+EssSummary.__doc__ = """lr_ess_summary's results.  mean, ess, act (in samples), se_mean float64 and stop_lag int32: [C, K] per chain and
+column; pooled_mean, pooled_ess, rhat: [K]; n: rows kept per chain.  ESS and ACT are NaN, SE 0 and the stop lag 0 where a
+chain's column is constant after burn-in.  Device tensors."""
+
+
+def ess_summary(rows, n_samples, columns, burnin=0.1, max_lag=2000):
+    """Convergence summary of rows [>= n_samples, C, width] (lr_ess_summary): per chain and column Tracer's ESS, ACT,
+    SE of the mean and the lag its sum stopped at, and per column the pooled mean, the pooled ESS and the split R-hat.
+    Every chain drops its first int(burnin * n_samples) rows.  columns: the column indices to diagnose."""
+    torch = _torch()
+    lib = _hip.load()
+    rows = _dev(rows, torch.float64)
+    if rows.dim() != 3 or rows.shape[0] < int(n_samples):
+        raise ValueError("rows must be [>= n_samples, chains, width]")
+    S, C, W = int(n_samples), int(rows.shape[1]), int(rows.shape[2])
+    cols = np.ascontiguousarray(np.asarray(columns, dtype=np.int32).ravel())
+    K = int(cols.size)
+    cptr = cols.ctypes.data_as(_hip.c_vp) if K else None
+    nbytes = lib.lr_ess_summary_workspace_bytes(S, C, W, cptr, K, float(burnin), int(max_lag))
+    if nbytes < 0:
+        _hip.check(int(nbytes), "lr_ess_summary_workspace_bytes")
+    dev = rows.device
+    cs = torch.empty((K, C, 4), dtype=torch.float64, device=dev)
+    stop = torch.empty((K, C), dtype=torch.int32, device=dev)
+    col = torch.empty((K, 3), dtype=torch.float64, device=dev)
+    ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
+    rc = _hip.launch(lib.lr_ess_summary, dev, _hip.ptr(rows), S, C, W, cptr, K, float(burnin), int(max_lag), _hip.ptr(cs),
+                     _hip.ptr(stop), _hip.ptr(col), _hip.ptr(ws), ws.numel())
+    _hip.check(rc, "lr_ess_summary")
+    per = cs.permute(2, 1, 0)                                  # [4, C, K]
+    return EssSummary(per[0].contiguous(), per[1].contiguous(), per[2].contiguous(), per[3].contiguous(),
+                      stop.t().contiguous(), col[:, 0].contiguous(), col[:, 1].contiguous(), col[:, 2].contiguous(),
+                      S - int(burnin * S))
+
+
 def debug_draws(seed, chain, it, purpose, idx, kind, shape):
     """Device RNG probe: kind 0 u_a, 1 u_b, 2 normal, 3 gamma(shape) at (it, purpose, idx)."""
     torch = _torch()

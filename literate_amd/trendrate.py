@@ -78,6 +78,10 @@ class TrendRateEngine(ChainEngine):
                 O[:, 12 + 2 * n:] = logs.adequacy_rows(emp[0], emp[1], b, d)
         return out.reshape(lead + (out.shape[1],))
 
+    def ess_rows(self, rows):
+        """The trace rows as they are: posterior, likelihood, prior and the six parameters l_min .. gamma (columns 1-9)."""
+        return rows, list(range(1, 10)), ["it", "posterior", "likelihood", "prior"] + LOG_HEAD[6:12]
+
     def log_head(self):
         n = len(self.DT)
         return list(LOG_HEAD) + ["l_%s" % i for i in range(n)] + ["m_%s" % i for i in range(n)] + \
