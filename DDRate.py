@@ -29,6 +29,11 @@ def build_parser():
     p.add_argument('--ess', type=float, default=-1.0, help='after the run, write <stem>_ESS.tsv and <stem>_ESS_chains.tsv '
                    '(per-chain effective sample sizes and split R-hat of the logged parameters, this burn-in fraction '
                    'dropped per chain) beside the logs; computed on the GPU (extension)')
+    p.add_argument('--summary', type=float, default=-1.0, help='after the run, write <stem>_summary.tsv (birth, death, net '
+                   'rate, carrying capacity and niche fraction per time bin: mean and 95 %% HPD, with the empirical rates) and '
+                   '<stem>_summary_params.tsv (mean and HPD of the logged parameters) beside the logs, all chains pooled '
+                   'after this burn-in fraction is dropped from each; computed on the GPU from the resident trace '
+                   '(extension)')
     p.add_argument('--block', type=int, default=0, help='iterations per device window (logs are flushed once per window; '
                    'default: -p rounded up to ~50000)')
     return p
@@ -39,6 +44,11 @@ def main(argv=None):
     if args.ess != -1.0:
         from literate_amd.logs import ess_arg_error
         err = ess_arg_error(args.ess, args.n, args.s)
+        if err:
+            raise SystemExit(err)
+    if args.summary != -1.0:
+        from literate_amd.logs import summary_arg_error
+        err = summary_arg_error(args.summary, args.n, args.s, args.chains)
         if err:
             raise SystemExit(err)
     import torch
@@ -106,6 +116,9 @@ def main(argv=None):
     if args.ess != -1.0:
         from literate_amd.logs import write_run_ess
         write_run_ess(eng, n_local, args.chains, world, rank, args.ess, args.s, stem)
+    if args.summary != -1.0:
+        from literate_amd.logs import write_run_summary
+        write_run_summary(eng, n_local, args.chains, world, rank, args.summary, stem)
     eng.close()
     if world > 1:
         dist.barrier()

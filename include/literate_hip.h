@@ -228,6 +228,45 @@ int lr_ess_summary(const double* rows, int32_t n_samples, int32_t n_chains, int3
                    int32_t n_cols, double burnin, int32_t max_lag, double* chain_stats, int32_t* stop_lag,
                    double* col_stats, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- Posterior summary of the parametric samplers: mean and 95 % HPD of columns and of per-bin curves (plotDD.py
+ * make_vec_dict :11-57, utilities/logAverager.py :18-51: np.mean and calcHPD lib:25-41 of a log's columns) ---------------
+ * rows: [n_samples, n_chains, row_width] doubles, row (sample s, chain c) at rows + (s * n_chains + c) * row_width, as in
+ * lr_ess_summary.  Every chain drops its first int(burnin * n_samples) rows (0 <= burnin < 1, no cap).  pooled = 0: one
+ * group per chain (plotDD.py on one log), G = n_chains; pooled = 1: one group, the kept rows pooled chain after chain
+ * (plotDD.py combine_logs :102-118), G = 1.  A group of n samples needs n_in = round-half-even(0.95 n) >= 2 and n < 2^31
+ * (else LR_ERR_SIZE).  A value triple is (mean, HPD low, HPD high) by calcHPD's rule: the column sorted, the first window of
+ * n_in values of minimum width (strict <), its two ends returned as sample values; mean = a fixed-order sum of the sorted
+ * column / n (no floating-point atomics: the same rows give the same bits).  A column that holds a NaN reports NaN in all
+ * three: the reference sorts a Python list, and a list sort of unordered values has no defined order, so its answer for
+ * such a column depends on where the NaN stood.  (-0.0 sorts below 0.0 here; the two compare equal.)  Infinities are
+ * values like any other: a window width inf - inf = NaN behaves as in calcHPD's scan (as the first width it is never
+ * replaced: window 0; as a later one it never compares below the minimum), the mean is what the sum gives.
+ *   lr_col_summary:   the triples of the n_cols columns cols[] (host, each in [0, row_width)) of any row table;
+ *                     out [G, n_cols, 3].
+ *   lr_curve_summary: per-bin curves derived on the device from the parameter vector rows[..., arg_col : arg_col + npar]
+ *                     by the functions the log columns come from (lr_dd_rates / lr_trend_rates: the same doubles);
+ *                     out [G, kinds, 3, n_bins], 1 <= n_bins <= LR_MAX_BINS.
+ *                     sampler 1 (DDRate.py, npar 8, aux = DT [n_bins], m_birth / m_death as lr_dd_rates): kinds 0 birth,
+ *                     1 death, 2 net = birth - death, 3 niche, 4 nicheFrac; sampler 2 (trend_rate.py, npar 6, aux = TREND
+ *                     [n_bins], m_birth / m_death = the -const_B / -const_D flags): kinds 0 birth, 1 death, 2 net.
+ *                     Another sampler (or DDRate model ids outside lr_dd_rates') is LR_ERR_MODEL.
+ * Workspace: the size queries check the arguments on the host first; the size itself asks the current device (the sort's
+ * temporary storage): LR_ERR_STATE when there is none.  per_pass = 0 asks for the whole problem in one pass, k > 0 for
+ * passes of k columns / bins.  A workspace smaller than the whole problem's makes the call work through the columns / bins
+ * in chunks - also where one pass would exceed the sort's 32-bit counts - down to one per pass (LR_ERR_WORKSPACE below
+ * that), with the same results bit for bit.                                                                              */
+int64_t lr_col_summary_workspace_bytes(int32_t n_samples, int32_t n_chains, int32_t row_width, const int32_t* cols,
+                                       int32_t n_cols, double burnin, int32_t pooled, int32_t cols_per_pass);
+int lr_col_summary(const double* rows, int32_t n_samples, int32_t n_chains, int32_t row_width, const int32_t* cols,
+                   int32_t n_cols, double burnin, int32_t pooled, double* out, void* workspace, int64_t workspace_bytes,
+                   void* stream);
+int64_t lr_curve_summary_workspace_bytes(int32_t n_samples, int32_t n_chains, int32_t row_width, int32_t arg_col,
+                                         int32_t sampler, int32_t n_bins, double burnin, int32_t pooled,
+                                         int32_t bins_per_pass);
+int lr_curve_summary(const double* rows, int32_t n_samples, int32_t n_chains, int32_t row_width, int32_t arg_col,
+                     int32_t sampler, int32_t m_birth, int32_t m_death, const double* aux, int32_t n_bins, double burnin,
+                     int32_t pooled, double* out, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- A11: fused multi-chain RJMCMC --------------------------------------------------------
  * Replaces runMCMC (LRF:216-373) for n_chains independent chains.  Per iteration: one scan of
  * the lineage arrays scoring every chain's proposal, then one chain-step kernel (reduce,

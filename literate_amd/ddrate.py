@@ -10,7 +10,7 @@ import csv
 import numpy as np
 
 from . import ops
-from .engine import ChainEngine
+from .engine import ChainEngine, posterior_summary_of
 from .literate_library import calculate_r_squared, create_bins
 
 LOG_HEAD = ["it", "posterior", "likelihood", "likelihood_birth", "likelihood_death", "prior", "l_max", "steepness_k",
@@ -75,6 +75,13 @@ class DDRateEngine(ChainEngine):
         out[..., 6] += self.origin                # DD:224
         out[..., 8] += out[..., 7]                # DD:225
         return out, list(range(1, 12)), ["it", "posterior", "likelihood", "prior"] + LOG_HEAD[6:14]
+
+    def posterior_summary(self, burnin=0.2, pooled=True, workspace_bytes=None, rows=None):
+        """Mean and 95 % HPD of the rows sampled so far (what plotDD.py takes of the logs, lr_curve_summary /
+        lr_col_summary on the resident trace): birth, death, net, niche and nicheFrac per time bin, and the log's
+        posterior, likelihood, prior and parameter columns -> PosteriorSummary.  rows: device trace rows [samples, chains,
+        LR_TRACE_W] to summarise instead (the rows of several ranks gathered)."""
+        return posterior_summary_of(self, 1, self.DT, self.m_birth, self.m_death, burnin, pooled, workspace_bytes, rows)
 
     def log_head(self):
         n = len(self.DT)

@@ -6,6 +6,7 @@ All chain state lives in one torch uint8 workspace in HBM whose layout the C ABI
 import ctypes as C
 import hashlib
 import os
+from collections import namedtuple
 
 import numpy as np
 
@@ -473,6 +474,23 @@ class ChainEngine:
         n_avail = self.samples_done()
         n = n_avail if n_samples is None else min(n_samples, n_avail)
         return self.trace[:n].cpu().numpy()
+
+
+PosteriorSummary = namedtuple("PosteriorSummary", "curves params names")
+PosteriorSummary.__doc__ = """An engine's posterior_summary: curves (ops.CurveSummary: per-bin mean and HPD of every kind), params
+(ops.ColSummary of the log's posterior, likelihood, prior and parameter columns) and the names of params' columns."""
+
+
+def posterior_summary_of(eng, sampler, aux, m_birth, m_death, burnin, pooled, workspace_bytes=None, rows=None):
+    """posterior_summary of the parametric samplers' engines (DDRateEngine, TrendRateEngine): the curves from the engine's
+    resident trace (or `rows`), the parameters from ess_rows' table (the log's terms)."""
+    eng.check_status()
+    S = eng.samples_done() if rows is None else int(rows.shape[0])
+    trace = eng.trace[:S] if rows is None else rows
+    curves = ops.curve_summary(trace, S, sampler, aux, m_birth, m_death, 4, burnin, pooled, workspace_bytes)
+    rows, cols, head = eng.ess_rows(trace)
+    params = ops.col_summary(rows, S, cols, burnin, pooled, workspace_bytes)
+    return PosteriorSummary(curves, params, [head[c] for c in cols])
 
 
 def split_trace_row(row):

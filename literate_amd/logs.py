@@ -519,3 +519,71 @@ def write_run_ess(eng, n_local, total_chains, world, rank, burnin, s_freq, stem)
     res = ops.ess_summary(rows, S, cols, burnin=burnin)
     host = res._replace(**{k: getattr(res, k).cpu().numpy() for k in res._fields if k != "n"})
     print(write_ess_tables(stem, [head[c] for c in cols], host, s_freq))
+
+
+# plotDD.py's vector names (make_vec_dict :29-55) and, in the same pattern, the two kinds it does not plot
+SUMMARY_KIND_HEAD = {"birth": ["birth_rate", "birth_minHPD", "birth_maxHPD"], "death": ["death_rate", "death_minHPD", "death_maxHPD"],
+                     "niche": ["niche", "niche_minHPD", "niche_maxHPD"], "net": ["net_rate", "net_minHPD", "net_maxHPD"],
+                     "nicheFrac": ["nicheFrac", "nicheFrac_minHPD", "nicheFrac_maxHPD"]}
+SUMMARY_KIND_ORDER = ["birth", "death", "niche", "net", "nicheFrac"]
+SUMMARY_PARAM_HEAD = ["parameter", "mean", "minHPD", "maxHPD"]
+
+
+def summary_arg_error(burnin, n_iterations, s_freq, n_chains):
+    """Why a CLI's --summary BURNIN cannot run (None when it can): a burn-in fraction outside [0, 1), or fewer than 2 of
+    the pooled samples inside the 95 % HPD window (calcHPD raises there): n = chains x (S - int(BURNIN * S)) with
+    S = ceil(n / s), window round(0.95 n)."""
+    if not (0.0 <= burnin < 1.0):
+        return "--summary takes a burn-in fraction in [0, 1)"
+    S = (n_iterations + s_freq - 1) // s_freq if n_iterations > 0 and s_freq > 0 else 0
+    n = max(n_chains, 0) * (S - int(burnin * S))
+    if int(round(0.95 * n)) < 2:
+        return "--summary %s keeps %d samples of %d chains x %d: the 95 %% HPD needs at least 2 inside its window" % (
+            burnin, n, n_chains, S)
+    return None
+
+
+def write_summary_tables(stem, origin, DT, n_spec, n_exti, kinds, values, param_names, params):
+    """<stem>_summary.tsv: one line per time bin i - time (origin + i + 0.5, plotDD.py:14), net_diversity (DT), emp_birth,
+    emp_death (N / DT, the first entry nan: plotDD.py:15-17), then mean, minHPD, maxHPD of every kind under plotDD.py's
+    names (SUMMARY_KIND_HEAD, in SUMMARY_KIND_ORDER); <stem>_summary_params.tsv: parameter, mean, minHPD, maxHPD.
+    values [kinds, (mean, lo, hi), n_bins] and params [columns, (mean, lo, hi)]: host arrays of one group of
+    ops.curve_summary / ops.col_summary.  Numbers as str(float), as the logs write them."""
+    DT = np.asarray(DT, dtype=float)
+    nb = len(DT)
+    with np.errstate(all="ignore"):
+        emp_b, emp_d = np.asarray(n_spec, dtype=float) / DT, np.asarray(n_exti, dtype=float) / DT
+    emp_b[0] = emp_d[0] = np.nan
+    head = ["time", "net_diversity", "emp_birth", "emp_death"]
+    cols = [float(origin) + np.arange(nb) + .5, DT, emp_b, emp_d]
+    for kind in SUMMARY_KIND_ORDER:
+        if kind in kinds:
+            head += SUMMARY_KIND_HEAD[kind]
+            cols += [values[list(kinds).index(kind), s] for s in range(3)]
+    with open(stem + "_summary.tsv", "w") as f:
+        f.write("\t".join(head) + "\n")
+        for i in range(nb):
+            f.write("\t".join(str(float(c[i])) for c in cols) + "\n")
+    with open(stem + "_summary_params.tsv", "w") as f:
+        f.write("\t".join(SUMMARY_PARAM_HEAD) + "\n")
+        for k, name in enumerate(param_names):
+            f.write("\t".join([name] + [str(float(v)) for v in params[k]]) + "\n")
+
+
+def write_run_summary(eng, n_local, total_chains, world, rank, burnin, stem):
+    """The CLIs' --summary: the engine's posterior_summary pooled over all chains of the rows the run sampled ->
+    <stem>_summary.tsv and <stem>_summary_params.tsv on rank 0.  The rows are gathered to rank 0's device once, so any
+    number of ranks writes the same bytes."""
+    from . import dist as lrd
+    S = eng.samples_done()
+    local = eng.trace[:S][:, :n_local]
+    rows = lrd.gather_traces(local.contiguous(), total_chains) if world > 1 else local
+    if rank != 0:
+        return
+    res = eng.posterior_summary(burnin, pooled=True, rows=rows)
+    P = res.params
+    params = np.stack([P.mean[0].cpu().numpy(), P.lo[0].cpu().numpy(), P.hi[0].cpu().numpy()], axis=1)
+    write_summary_tables(stem, eng.origin, eng.DT, eng.n_spec, eng.n_exti, res.curves.kinds,
+                         res.curves.values[0].cpu().numpy(), res.names, params)
+    print("posterior summary of %d samples (%d chains pooled): %s_summary.tsv, %s_summary_params.tsv" % (
+        res.curves.n, total_chains, stem, stem))

@@ -468,6 +468,90 @@ def ess_summary(rows, n_samples, columns, burnin=0.1, max_lag=2000):
                       S - int(burnin * S))
 
 
+ColSummary = namedtuple("ColSummary", "mean lo hi n")
+ColSummary.__doc__ = """lr_col_summary's results.  mean, lo, hi [G, K]: the mean and the ends of the 95 % HPD of each chosen column (NaN
+where the column holds a NaN); n: samples per group.  G = 1 pooled, one per chain otherwise.  Device tensors."""
+
+CurveSummary = namedtuple("CurveSummary", "kinds values n")
+CurveSummary.__doc__ = """lr_curve_summary's results.  kinds: the names of values' second axis (CURVE_KINDS[sampler]); values [G, kinds,
+3 (mean, HPD low, HPD high), n_bins] (device); n: samples per group.  G = 1 pooled, one per chain otherwise."""
+
+CURVE_KINDS = {1: ("birth", "death", "net", "niche", "nicheFrac"), 2: ("birth", "death", "net")}
+
+
+def summary_geometry(n_samples, n_chains, burnin, pooled):
+    """(rows dropped per chain, samples per group n, samples inside the HPD window) of lr_col_summary /
+    lr_curve_summary: int(burnin * S) rows dropped, n_in = round-half-even(0.95 n).  Host arithmetic only."""
+    S = int(n_samples)
+    burn = int(burnin * S)
+    n = (S - burn) * (int(n_chains) if pooled else 1)
+    return burn, n, int(round(0.95 * n))
+
+
+def _summary_cap(workspace_bytes, dev, torch):
+    # by default at most a quarter of the free device memory (and never less than 1 GiB), as ops.rtt_summary
+    if workspace_bytes is not None:
+        return int(workspace_bytes)
+    return max(1 << 30, torch.cuda.mem_get_info(dev)[0] // 4)
+
+
+def col_summary(rows, n_samples, columns, burnin=0.2, pooled=True, workspace_bytes=None):
+    """Mean and 95 % HPD (calcHPD) of chosen columns of rows [>= n_samples, C, width] (lr_col_summary: what plotDD.py /
+    logAverager.py take of a log's parameter columns) -> ColSummary.  Every chain drops its first int(burnin * n_samples)
+    rows; pooled: the kept rows of all chains as one sample, chain after chain; else one summary per chain.
+    workspace_bytes: cap the workspace (the call then works through the columns in chunks; the same results)."""
+    torch = _torch()
+    lib = _hip.load()
+    rows = _dev(rows, torch.float64)
+    if rows.dim() != 3 or rows.shape[0] < int(n_samples):
+        raise ValueError("rows must be [>= n_samples, chains, width]")
+    S, C, W = int(n_samples), int(rows.shape[1]), int(rows.shape[2])
+    cols = np.ascontiguousarray(np.asarray(columns, dtype=np.int32).ravel())
+    K = int(cols.size)
+    cptr = cols.ctypes.data_as(_hip.c_vp) if K else None
+    full = lib.lr_col_summary_workspace_bytes(S, C, W, cptr, K, float(burnin), int(bool(pooled)), 0)
+    if full < 0:
+        _hip.check(int(full), "lr_col_summary_workspace_bytes")
+    dev = rows.device
+    G = 1 if pooled else C
+    out = torch.empty((G, K, 3), dtype=torch.float64, device=dev)
+    ws = torch.empty(max(1, min(int(full), _summary_cap(workspace_bytes, dev, torch))), dtype=torch.uint8, device=dev)
+    rc = _hip.launch(lib.lr_col_summary, dev, _hip.ptr(rows), S, C, W, cptr, K, float(burnin), int(bool(pooled)),
+                     _hip.ptr(out), _hip.ptr(ws), ws.numel())
+    _hip.check(rc, "lr_col_summary")
+    return ColSummary(out[:, :, 0].contiguous(), out[:, :, 1].contiguous(), out[:, :, 2].contiguous(),
+                      summary_geometry(S, C, burnin, pooled)[1])
+
+
+def curve_summary(rows, n_samples, sampler, aux, m_birth, m_death, arg_col=4, burnin=0.2, pooled=True,
+                  workspace_bytes=None):
+    """Mean and 95 % HPD per time bin of the curves the parameter vectors rows[..., arg_col:arg_col + npar] imply
+    (lr_curve_summary: what plotDD.py takes of a log's l_i, m_i and niche_i columns, derived on the device instead of read
+    from the log) -> CurveSummary.  sampler 1: DDRate (aux = DT, m_birth / m_death as dd_rates; birth, death, net, niche,
+    nicheFrac); sampler 2: trend_rate (aux = TREND, m_birth / m_death = const_birth / const_death; birth, death, net).
+    Burn-in, pooling and workspace_bytes as col_summary (chunks of bins)."""
+    torch = _torch()
+    lib = _hip.load()
+    rows = _dev(rows, torch.float64)
+    if rows.dim() != 3 or rows.shape[0] < int(n_samples):
+        raise ValueError("rows must be [>= n_samples, chains, width]")
+    aux = _dev(aux, torch.float64, rows.device).reshape(-1)
+    S, C, W, nb = int(n_samples), int(rows.shape[1]), int(rows.shape[2]), int(aux.numel())
+    sampler = int(sampler)
+    full = lib.lr_curve_summary_workspace_bytes(S, C, W, int(arg_col), sampler, nb, float(burnin), int(bool(pooled)), 0)
+    if full < 0:
+        _hip.check(int(full), "lr_curve_summary_workspace_bytes")
+    dev = rows.device
+    G = 1 if pooled else C
+    kinds = CURVE_KINDS[sampler]
+    out = torch.empty((G, len(kinds), 3, nb), dtype=torch.float64, device=dev)
+    ws = torch.empty(max(1, min(int(full), _summary_cap(workspace_bytes, dev, torch))), dtype=torch.uint8, device=dev)
+    rc = _hip.launch(lib.lr_curve_summary, dev, _hip.ptr(rows), S, C, W, int(arg_col), sampler, int(m_birth), int(m_death),
+                     _hip.ptr(aux), nb, float(burnin), int(bool(pooled)), _hip.ptr(out), _hip.ptr(ws), ws.numel())
+    _hip.check(rc, "lr_curve_summary")
+    return CurveSummary(kinds, out, summary_geometry(S, C, burnin, pooled)[1])
+
+
 def debug_draws(seed, chain, it, purpose, idx, kind, shape):
     """Device RNG probe: kind 0 u_a, 1 u_b, 2 normal, 3 gamma(shape) at (it, purpose, idx)."""
     torch = _torch()

@@ -6,7 +6,7 @@ import csv
 import numpy as np
 
 from . import ops
-from .engine import ChainEngine
+from .engine import ChainEngine, posterior_summary_of
 from .literate_library import calculate_r_squared, create_bins
 
 SMALL_NUMBER = 0.000000000000001
@@ -81,6 +81,13 @@ class TrendRateEngine(ChainEngine):
     def ess_rows(self, rows):
         """The trace rows as they are: posterior, likelihood, prior and the six parameters l_min .. gamma (columns 1-9)."""
         return rows, list(range(1, 10)), ["it", "posterior", "likelihood", "prior"] + LOG_HEAD[6:12]
+
+    def posterior_summary(self, burnin=0.2, pooled=True, workspace_bytes=None, rows=None):
+        """Mean and 95 % HPD of the rows sampled so far (lr_curve_summary / lr_col_summary on the resident trace): birth,
+        death and net rate per time bin, and the log's posterior, likelihood, prior and parameter columns ->
+        engine.PosteriorSummary.  rows: device trace rows [samples, chains, LR_TRACE_W] to summarise instead."""
+        return posterior_summary_of(self, 2, self.trend, self.const_birth, self.const_death, burnin, pooled,
+                                    workspace_bytes, rows)
 
     def log_head(self):
         n = len(self.DT)
