@@ -56,6 +56,14 @@ def build_parser():
                    'mean and effective sample size, the lowest chain ESS, split R-hat) and <stem>_ESS_chains.tsv (ESS, '
                    'autocorrelation time and SE of the mean per chain and column) next to the logs, with this burn-in '
                    'fraction dropped per chain (what the tutorial checks in Tracer); computed on the GPU')
+    p.add_argument('--ppc', type=float, default=-1.0, help='after the run, write <stem>_PPC.tsv and <stem>_PPC_fit.tsv next '
+                   'to the logs: a posterior predictive check that simulates lineages forward under --ppc_draws posterior '
+                   'draws of the rates (this burn-in fraction dropped per chain) and sets the predicted births, deaths and '
+                   'diversity per bin beside the observed ones; simulated on the GPU')
+    p.add_argument('--ppc_draws', type=int, default=1000, help='posterior draws the check simulates under')
+    p.add_argument('--ppc_scale', type=int, default=100, help='simulation steps per time unit (the reference Simulator.scale)')
+    p.add_argument('--ppc_start_bin', type=int, default=-1, help='bin at whose left edge the free-running simulations start '
+                   '(default: the first bin after bin 0 that starts with an observed lineage)')
     p.add_argument('--init_shifts', type=int, default=0, help='initial number of rate shifts per process')
     p.add_argument('--block', type=int, default=0, help='iterations per device window: logs are written and flushed and '
                    'the state is printed once per window, while the next one runs (default: -p rounded up to ~50000)')
@@ -102,6 +110,13 @@ def main(argv=None):
         err = ess_arg_error(args.ess, args.n, args.s)
         if err:
             raise SystemExit(err)
+    if args.ppc != -1.0:
+        from literate_amd.ppc import arg_error
+        err = arg_error(args.ppc, args.model_BDI, args.pyrate_output)
+        if err:
+            raise SystemExit(err)
+        if args.ppc_draws < 1 or args.ppc_scale < 1:
+            raise SystemExit("--ppc_draws and --ppc_scale must be at least 1")
     print("\n\n             LiteRate - 20200206 (MI355X engine)\n")
     import torch
     import torch.distributed as dist
@@ -224,6 +239,11 @@ def main(argv=None):
     if args.ess != -1.0:
         stem = logs.log_paths(args.d, args.model_BDI, args.out)[1]["div"][:-len("_div.log")]
         logs.write_run_ess(eng, n_local, args.chains, world, rank, args.ess, args.s, stem)
+    if args.ppc != -1.0 and n_samples:
+        from literate_amd import ppc
+        stem = logs.log_paths(args.d, args.model_BDI, args.out)[1]["div"][:-len("_div.log")]
+        ppc.write_run_ppc(eng, sp, ex, n_local, args.chains, world, rank, args.ppc, args.ppc_draws, args.ppc_scale, rseed,
+                          stem, start_bin=args.ppc_start_bin if args.ppc_start_bin >= 0 else None)
     eng.close()
     if world > 1:
         dist.destroy_process_group()

@@ -167,6 +167,34 @@ int lr_simulate_bd(const double* lam_steps, const double* mu_steps, int32_t n_st
                    uint64_t seed, double* ts, double* te, int64_t* counters /* [4] */,
                    int64_t* alive_trace, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- Batched simulator: many independent mode-0 runs of the scheme above in one launch (the replicates of a posterior
+ * predictive check).  Replicate r < n_reps IS the run lr_simulate_bd(lam_steps, mu_steps, n_steps = n_bins * steps_per_bin,
+ * mode 0, ..., n_start[r], capacity, seed + r) with lam_steps[t] = lam_bins[r, t / steps_per_bin] / (double) steps_per_bin
+ * (likewise mu): the same draws at the same addresses - key ((uint32) (seed + r), lineage slot), counter (t, 24, 0), first
+ * uniform - and the same thresholds, so its counts equal that run's bit for bit.  Outputs, exact integers (nothing per
+ * lineage is written):
+ *   counts [n_reps, 4, n_bins]: per bin b, 0 births during its steps (founders are not births), 1 deaths during its steps,
+ *                               2 living at the start of its first step, 3 lineage-steps (the living count summed over its
+ *                               steps; / steps_per_bin = branch length in time units);
+ *   totals [n_reps, 4]:         lineages created incl. founders, living after the last step, overflow flag, the first step
+ *                               at whose start nobody lived or -1.
+ * capacity: the most lineages ONE replicate may create, 1 .. 2^31 - 1 (the slot is a 32-bit key).  A replicate that would
+ * exceed it sets its overflow flag; its counts are then unspecified and no other replicate is affected.  n_start [n_reps]
+ * lives on the device: a value < 1 or > capacity makes that replicate report overflow and nothing else.  An extinct
+ * replicate carries zeros on.  The result of a replicate depends on (seed + r, its two rate rows, n_start[r], capacity)
+ * only.  One workgroup per replicate at a time, at most LR_SIMBATCH_GROUPS workgroups; the living lineages are a list of
+ * slot numbers whose first LR_SIMBATCH_LDS_SLOTS positions sit in LDS, the rest in the workgroup's slice of the workspace.
+ * LR_ERR_SIZE: n_reps / n_bins / steps_per_bin < 1, n_bins > LR_MAX_BINS, n_bins * steps_per_bin >= 2^31, capacity outside
+ * its range.  The size query is host arithmetic (no device); a smaller workspace is LR_ERR_WORKSPACE.                    */
+#define LR_SIMBATCH_GROUPS 512
+#define LR_SIMBATCH_LDS_SLOTS 16384
+int64_t lr_simulate_bd_batch_workspace_bytes(int32_t n_reps, int32_t n_bins, int32_t steps_per_bin, int64_t capacity);
+int lr_simulate_bd_batch(const double* lam_bins /* [n_reps, n_bins] */, const double* mu_bins /* [n_reps, n_bins] */,
+                         int32_t n_reps, int32_t n_bins, int32_t steps_per_bin,
+                         const int64_t* n_start /* [n_reps] */, int64_t capacity, uint64_t seed,
+                         int64_t* counts /* [n_reps, 4, n_bins] */, int64_t* totals /* [n_reps, 4] */,
+                         void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- the text form of the logs (host only, no GPU) ---------------------------------
  * The reference writes every number through Python's csv module (LRF:334-359, DD:236-238): str(float), the shortest
  * decimal string that reads back to the same double, "24.0" / "1e-05" / "1.5e+16" by Python's rules.  lr_format_rows

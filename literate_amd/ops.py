@@ -377,6 +377,42 @@ def simulate_bd(n_start, n_steps, seed, lam_steps=None, mu_steps=None, mode=0, l
     return ts[:n], te[:n], trace
 
 
+def simulate_bd_batch(lam_bins, mu_bins, steps_per_bin, n_start, seed, capacity=None, device=None):
+    """Many independent birth-death simulations in one launch (lr_simulate_bd_batch).  lam_bins, mu_bins [n_reps, n_bins]:
+    rates per time unit; replicate r is simulate_bd(n_start[r], n_bins * steps_per_bin, seed + r, lam_bins[r, t //
+    steps_per_bin] / steps_per_bin, ...) bit for bit.  n_start: an int or [n_reps].  Returns (counts int64 [n_reps, 4,
+    n_bins]: births, deaths, living at the bin's start, lineage-steps; totals int64 [n_reps, 4]: created, living at the
+    end, overflow flag, first empty step or -1) as device tensors.  capacity (per replicate): default max(64 x max
+    n_start, 1M); a replicate that exceeds it only sets its flag - nothing is raised, the flags are the caller's to read."""
+    torch = _torch()
+    lib = _hip.load()
+    lam = _dev(lam_bins, torch.float64, device)
+    dev = lam.device
+    mu = _dev(mu_bins, torch.float64, dev)
+    if lam.dim() != 2 or mu.shape != lam.shape:
+        raise ValueError("lam_bins and mu_bins must both be [n_reps, n_bins]")
+    R, nb = int(lam.shape[0]), int(lam.shape[1])
+    if isinstance(n_start, (int, np.integer)):
+        most = int(n_start)
+        n0 = torch.full((R,), most, dtype=torch.int64, device=dev)
+    else:
+        n0 = _dev(n_start, torch.int64, dev).reshape(-1)
+        if n0.numel() != R:
+            raise ValueError("n_start must be an int or hold one entry per replicate")
+        most = int(n0.max()) if capacity is None and R else 0
+    capacity = int(capacity or max(64 * most, 1 << 20))
+    nbytes = lib.lr_simulate_bd_batch_workspace_bytes(R, nb, int(steps_per_bin), capacity)
+    if nbytes < 0:
+        _hip.check(int(nbytes), "lr_simulate_bd_batch_workspace_bytes")
+    counts = torch.empty((R, 4, nb), dtype=torch.int64, device=dev)
+    totals = torch.empty((R, 4), dtype=torch.int64, device=dev)
+    ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
+    rc = _hip.launch(lib.lr_simulate_bd_batch, dev, _hip.ptr(lam), _hip.ptr(mu), R, nb, int(steps_per_bin), _hip.ptr(n0),
+                     capacity, int(seed) & 0xFFFFFFFFFFFFFFFF, _hip.ptr(counts), _hip.ptr(totals), _hip.ptr(ws), ws.numel())
+    _hip.check(rc, "lr_simulate_bd_batch")
+    return counts, totals
+
+
 RttSummary = namedtuple("RttSummary", "time rates shift_freq k_counts n_samples")
 RttSummary.__doc__ = """lr_rtt_summary's results.  time [n_bins] (host): bin centres in ascending time; rates [G, 3, 3, n_bins]:
 (birth, death, net) x (mean, HPD low, HPD high); shift_freq [G, 2, n_bins]; k_counts int64 [G, 2, LR_KMAX] (K = 1 ..
