@@ -466,7 +466,8 @@ int lr_mcmc_steps(lr_engine* e, int64_t n_iters, void* stream);
  * with the SAME configuration (hence the same lr_mcmc_layout) into this engine's workspace, then calls this
  * instead of lr_mcmc_init: it rebuilds what holds device addresses or derives from the data (argument blob,
  * log(br_length), packed lineage indices), forgets what earlier launches left in the engine's scratch regions (status,
- * warnings, carried scan sums) and leaves the chains alone.  Chain state written into the workspace from outside
+ * carried scan sums), keeps the warning word the restored workspace carries (the rows that raised it are still in
+ * its trace) and leaves the chains alone.  Chain state written into the workspace from outside
  * must always be followed by this call.                                                                          */
 int lr_mcmc_restore(lr_engine* e, void* stream);
 /* measurement hook (bench.py roofline): average duration in ms of `reps` back-to-back launches of
@@ -481,7 +482,7 @@ int lr_mcmc_status(lr_engine* e, int32_t* status /* host */, void* stream);
 /* Blocks until `stream` is idle and copies the engine's warning word to *warnings (host): a bit set of LR_WARN_*.
  * LR_WARN_KCAP: at least one add-shift move (LRF:29-47) was proposed from a state that already holds LR_KMAX rates and
  * was rejected for that reason alone - the reference has no such cap, the posterior on the number of shifts is
- * truncated at LR_KMAX.  Cleared by lr_mcmc_init / lr_mcmc_restore.                                                  */
+ * truncated at LR_KMAX.  Cleared by lr_mcmc_init; lr_mcmc_restore keeps the word of the workspace it resumes.        */
 #define LR_WARN_KCAP 2
 int lr_mcmc_warnings(lr_engine* e, int32_t* warnings /* host */, void* stream);
 /* measurement hook: name of the kernel lr_mcmc_steps spends its time in, as a kernel trace prints it (n >= 64). */

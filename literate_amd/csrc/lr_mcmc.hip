@@ -1424,10 +1424,16 @@ __global__ void lr_dd_consts_kernel(const double* __restrict__ DT, int n_bins, d
 }
 
 // everything in the workspace that holds device addresses or derives from the data alone
-static void lr_prepare_constants(const lr_engine* e, const lr_step_args& a, hipStream_t stream) {
-    // a fresh or restored run starts with a clear status and warning word (a checkpoint never carries a void run on:
-    // ChainEngine.save refuses to write one)
-    (void)hipMemsetAsync(e->ws + e->lay.status, 0, 256, stream);
+static void lr_prepare_constants(const lr_engine* e, const lr_step_args& a, hipStream_t stream, bool restored) {
+    // a fresh or restored run starts with a clear status word (a checkpoint never carries a void run on:
+    // ChainEngine.save refuses to write one).  A fresh run clears the warning word behind it too; a restored one keeps
+    // the checkpoint's: its trace still holds the rows of the iterations that raised LR_WARN_KCAP.
+    if (restored) {
+        (void)hipMemsetAsync(e->ws + e->lay.status, 0, 4, stream);
+        (void)hipMemsetAsync(e->ws + e->lay.status + 8, 0, 248, stream);
+    } else {
+        (void)hipMemsetAsync(e->ws + e->lay.status, 0, 256, stream);
+    }
     // ... and nothing carried over from the launches before it (four-chain kernel)
     if (e->lay.persistent == 2) (void)hipMemsetAsync(e->ws + e->lay.xchg, 0, (size_t)((e->cfg.n_chains + 3) / 4) * LR_P4_CARRY_BYTES, stream);
     hipLaunchKernelGGL(lr_log_br_kernel, dim3((e->cfg.n_bins + 127) / 128), dim3(128), 0, stream, e->br_length,
@@ -1457,7 +1463,7 @@ extern "C" int lr_mcmc_restore(lr_engine* e, void* stream_) {
     if (!e) return LR_ERR_NULL;
     hipStream_t stream = (hipStream_t)stream_;
     const lr_step_args a = lr_make_args(e);
-    lr_prepare_constants(e, a, stream);
+    lr_prepare_constants(e, a, stream, true);
     int rc = (int)hipGetLastError();
     if (rc) return rc;
     if (e->persistent) rc = lr_pack_lineages(e, stream);
@@ -1476,7 +1482,7 @@ extern "C" int lr_mcmc_init(lr_engine* e, const double* L, const double* M, cons
     if (L && e->cfg.sampler != 0 && kmax < LR_DD_NPAR) return LR_ERR_SIZE;
     hipStream_t stream = (hipStream_t)stream_;
     const lr_step_args a = lr_make_args(e);
-    lr_prepare_constants(e, a, stream);
+    lr_prepare_constants(e, a, stream, false);
     if (e->persistent) {
         const int rcp = lr_pack_lineages(e, stream);
         if (rcp) return rcp;

@@ -113,11 +113,27 @@ def bin_events(ts, te, win_lo, win_hi):
     return sp, ex, br
 
 
+def _check_host_K(K, kmax, what, room=None):
+    """K given as a host array: 1 <= K <= kmax (and K + 1 <= kmax where `room` marks an add move), or ValueError - the
+    kernels index the padded rows by K unchecked.  A K that already lives on the device is not read back."""
+    if hasattr(K, "is_cuda") and K.is_cuda:
+        return
+    k = np.asarray(K.cpu().numpy() if hasattr(K, "detach") else K).astype(np.int64).ravel()
+    if k.size and (k.min() < 1 or k.max() > kmax):
+        raise ValueError("%s: K must lie in 1..kmax = %d (got %d..%d)" % (what, kmax, k.min(), k.max()))
+    if room is not None:
+        room = np.asarray(room.cpu().numpy() if hasattr(room, "detach") else room).ravel()
+        if room.shape == k.shape and np.any(room & (k + 1 > kmax)):
+            raise ValueError("%s: an add move at K = kmax = %d has no room for the new rate" % (what, kmax))
+
+
 def expand_rates(rates, times, K, n_bins, mode=0):
-    """[C,n_bins] per-bin rates from K segment rates (get_rate_index + L[ind], LRF:125-135)."""
+    """[C,n_bins] per-bin rates from K segment rates (get_rate_index + L[ind], LRF:125-135).  K as a host array is
+    checked against kmax (ValueError); a device-resident K is passed on unchecked."""
     torch = _torch()
     lib = _hip.load()
     rates, times = _dev(rates, torch.float64), _dev(times, torch.float64)
+    _check_host_K(K, rates.shape[1], "expand_rates")
     K = _dev(K, torch.int32)
     C, kmax = rates.shape
     if times.shape != (C, kmax + 1) or K.shape != (C,):
@@ -249,10 +265,14 @@ class LoglikSession:
 
 def rj_propose_score(rates, times, K, move, index, draws, mult_d=1.1):
     """Batched explicit-draw proposal scorer (LRF:29-69, 165-176).  Returns
-    (rates'[C,kmax], times'[C,kmax+1], K'[C], score[C])."""
+    (rates'[C,kmax], times'[C,kmax+1], K'[C], score[C]).  K as a host array is checked (1 <= K <= kmax, and K + 1 <= kmax
+    for the add moves when `move` is a host array too: ValueError); a device-resident K is passed on unchecked."""
     torch = _torch()
     lib = _hip.load()
     rates, times = _dev(rates, torch.float64), _dev(times, torch.float64)
+    is_dev = hasattr(move, "is_cuda") and move.is_cuda
+    _check_host_K(K, rates.shape[1], "rj_propose_score",
+                  None if is_dev else (move.cpu().numpy() if hasattr(move, "detach") else np.asarray(move)) == 1)
     K, move, index = _dev(K, torch.int32), _dev(move, torch.int32), _dev(index, torch.int32)
     draws = _dev(draws, torch.float64)
     C, kmax = rates.shape
@@ -269,10 +289,13 @@ def rj_propose_score(rates, times, K, move, index, draws, mult_d=1.1):
 
 
 def log_priors(rates, K, shape, gamma_rate, poi_rate=None):
-    """out[C] = prior_gamma(rates[:K], shape, gamma_rate) (+ Poisson_prior(K, poi_rate)) (LRF:198-202)."""
+    """out[C] = prior_gamma(rates[:K], shape, gamma_rate) (+ Poisson_prior(K, poi_rate)) (LRF:198-202).  K as a host array
+    is checked against kmax (ValueError); a device-resident K is passed on unchecked."""
     torch = _torch()
     lib = _hip.load()
-    rates, K = _dev(rates, torch.float64), _dev(K, torch.int32)
+    rates = _dev(rates, torch.float64)
+    _check_host_K(K, rates.shape[1], "log_priors")
+    K = _dev(K, torch.int32)
     C, kmax = rates.shape
     g = _dev(gamma_rate, torch.float64)
     p = None if poi_rate is None else _dev(poi_rate, torch.float64)
