@@ -125,7 +125,9 @@ int lr_log_priors(const double* rates, const int32_t* K, int32_t kmax, int32_t n
 /* ---- A12: DDRate rates --------------------------------------------------------------------
  * Replaces the rate half of likelihood_function (DD:71-100): args [C,8] =
  * [l_max,k,x0,div_0,L,m_max,nuB,nuD] -> per-bin birth/death rates, niche, niche fraction
- * (each [C,n_bins]); the likelihood half is lr_bd_loglik_batch(model 2) on those rates.      */
+ * (each [C,n_bins]); the likelihood half is lr_bd_loglik_batch(model 2) on those rates.
+ * niche_frac ** nu is what numpy's power gives for every fraction >= 0, inf included, and every
+ * exponent (x ** 0 = 1 for every x); a negative fraction gives nan (csrc/lr_dd.h).             */
 int lr_dd_rates(const double* args, const double* DT, int32_t n_bins, int32_t n_chains,
                 int32_t m_birth, int32_t m_death,
                 double* birth_rates, double* death_rates, double* niche, double* niche_frac,

@@ -16,13 +16,20 @@ struct lr_dd_params {
     double l_max, k, x0, div_0, L, m_max, nuB, nuD;
 };
 
+// x ** nu from lx = lr_log(x), for the rate maps below: exp(nu * lx), a logarithm the two processes can share (a pow call
+// is a log and an exp plus its own special-case handling).  What numpy's power gives is reproduced for every base
+// x >= 0 (inf included) and every exponent: 0 ** nu = 0 for nu > 0 and inf for nu < 0, x ** 0 = 1 for EVERY x - the
+// select, since exp(0 * log 0) = exp(0 * -inf) would be nan - and nan for a nan base with nu != 0.  NOT reproduced:
+// a negative base gives nan here whatever the exponent (lr_log of a negative number), where numpy returns a real number
+// for an integer-valued one; DT >= 0, niche > 0 and TREND in (0, 1] - the support of the priors - never get there.
+// For nu != 0 the select passes the exp through: the same bits as without it.
+__device__ __forceinline__ double lr_pow_of_log(double lx, double nu) { return nu == 0.0 ? 1.0 : exp(nu * lx); }
+
 // likelihood_function's rate half for ONE bin (DD:71-100): x = bin index (TIME_RANGE, lib:255), dt = DT[b].
 // get_logistic (DD:55-56) raises its denominator to 1/nu with nu = 1: x ** 1.0 is x, so no pow here.
 __device__ __forceinline__ void lr_dd_bin_rates(const lr_dd_params& p, double x, double dt, int m_birth, int m_death,
                                                 double* br_, double* dr_, double* niche_, double* frac_) {
-    // frac ** nu as exp(nu * log(frac)) with the logarithm shared by the two processes when they see the same niche
-    // (a pow call is a log and an exp plus its own special-case handling; 0 and negative fractions behave as in
-    // numpy: 0 ** nu = 0, negative ** nu = nan)
+    // frac ** nu through lr_pow_of_log, with the logarithm shared by the two processes when they see the same niche
     double niche = 1.0, frac = 1.0, br, dr, lfrac = 0.0;
     int niche_model = 0;
     if (m_birth == 0) {
@@ -31,7 +38,7 @@ __device__ __forceinline__ void lr_dd_bin_rates(const lr_dd_params& p, double x,
         niche = (m_birth == 1) ? 1.0 * (p.L + p.div_0) : p.div_0 + p.L / (1.0 + exp(-p.k * (x - p.x0)));
         frac = dt / niche;
         lfrac = lr_log(frac), niche_model = m_birth;
-        br = p.l_max - p.l_max * exp(p.nuB * lfrac);
+        br = p.l_max - p.l_max * lr_pow_of_log(lfrac, p.nuB);
         if (br <= 0.0) br = LR_DD_SMALL;
     }
     if (m_death <= 0) {
@@ -42,7 +49,7 @@ __device__ __forceinline__ void lr_dd_bin_rates(const lr_dd_params& p, double x,
             frac = dt / niche;
             lfrac = lr_log(frac);
         }
-        dr = p.m_max + p.m_max * exp(p.nuD * lfrac);
+        dr = p.m_max + p.m_max * lr_pow_of_log(lfrac, p.nuD);
         if (dr <= 0.0) dr = LR_DD_SMALL;
     }
     *br_ = br, *dr_ = dr, *niche_ = niche, *frac_ = frac;
@@ -153,15 +160,15 @@ struct lr_trend_params {
 // likelihood_function's rate half for ONE bin (trend_rate.py:73-88); t = TREND[b]
 __device__ __forceinline__ void lr_trend_bin_rates(const lr_trend_params& p, double t, int const_birth, int const_death,
                                                    double* br_, double* dr_) {
-    // TREND ** exponent as exp(exponent * log(TREND)), one logarithm for both processes (TREND is in (0, 1])
+    // TREND ** exponent through lr_pow_of_log, one logarithm for both processes (TREND is in (0, 1])
     double br = 1.0 * p.l_min, dr = 1.0 * p.m_min;
     const double lt = (const_birth && const_death) ? 0.0 : lr_log(t);
     if (!const_birth) {
-        br = p.l_min + p.alpha * exp(p.delta * lt);
+        br = p.l_min + p.alpha * lr_pow_of_log(lt, p.delta);
         if (br <= 0.0) br = LR_DD_SMALL;
     }
     if (!const_death) {
-        dr = p.m_min + p.beta * exp(p.gamma * lt);
+        dr = p.m_min + p.beta * lr_pow_of_log(lt, p.gamma);
         if (dr <= 0.0) dr = LR_DD_SMALL;
     }
     *br_ = br, *dr_ = dr;

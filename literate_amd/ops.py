@@ -312,6 +312,8 @@ def dd_rates(args, DT, m_birth=2, m_death=2):
     args, DT = _dev(args, torch.float64), _dev(DT, torch.float64)
     if args.dim() == 1:
         args = args[None, :]
+    if args.shape[1] != 8:
+        raise ValueError("DDRate takes 8 parameters per state")
     C, n_bins = args.shape[0], DT.numel()
     outs = [torch.empty((C, n_bins), dtype=torch.float64, device=args.device) for _ in range(4)]
     rc = _hip.launch(lib.lr_dd_rates, args.device, _hip.ptr(args), _hip.ptr(DT), n_bins, C, m_birth, m_death, *[_hip.ptr(o) for o in outs])
