@@ -5,7 +5,9 @@
 
 Additive flags (not in the reference): --chains N (total chains; sharded over ranks when started
 with torch.distributed.run), --init_shifts K (start every chain with K equally spaced shifts per
-process and the CLI's Gamma(2,2) rates; SURVEY.md section 8c 'config-1 note').
+process and the CLI's Gamma(2,2) rates; SURVEY.md section 8c 'config-1 note'), --rtt BURNIN and --rtt_bf REPS
+(posterior rates through time, and the frequencies of rate shifts as Bayes factors against their Monte Carlo prior:
+what plotRJforward.v3.py derives from the logs, computed on the GPU).
 With --chains 1 the log file names are exactly the reference's; with more, chain k >= 0 writes
 <name>_c<k>_{mcmc,sp_rates,ex_rates}.log next to the shared _div.log.
 """
@@ -52,6 +54,14 @@ def build_parser():
                    'of the birth, death and net rates and the frequency of rate shifts per unit bin) and <stem>_RTT_K.tsv '
                    '(histogram of the number of rates) next to the logs, pooled over all chains with this burn-in fraction '
                    'dropped per chain (plotRJforward.v3.py -combine 1); computed on the GPU')
+    p.add_argument('--rtt_bf', type=int, default=0, metavar='REPS', help='with --rtt: also write <stem>_RTT_BF.tsv (the shift '
+                   'frequencies of <stem>_RTT.tsv as 2 ln Bayes factors against the prior on shift times, and the birth_BF2 / '
+                   'birth_BF6 / death_BF2 / death_BF6 vectors of plotRJforward.v3.py), <stem>_RTT_BF_prior.tsv (the prior '
+                   'frequency and the bf2 / bf6 thresholds) and <stem>_RTT_BF_K.tsv (prior and posterior of the number of '
+                   'rates); the prior is simulated over REPS replicates on the GPU (get_prior_shift runs 100000 on the host)')
+    p.add_argument('--rtt_bf_lambda', type=float, default=0.0, metavar='L', help='the prior --rtt_bf simulates: 0 = the '
+                   'Gamma(2, 1) hyper-prior on the Poisson rate that plotRJforward.v3.py hard-codes, L > 0 = that fixed '
+                   'rate (a run made with -Poisson_prior L)')
     p.add_argument('--ess', type=float, default=-1.0, help='after the run, write <stem>_ESS.tsv (per log column: pooled '
                    'mean and effective sample size, the lowest chain ESS, split R-hat) and <stem>_ESS_chains.tsv (ESS, '
                    'autocorrelation time and SE of the mean per chain and column) next to the logs, with this burn-in '
@@ -105,6 +115,11 @@ def main(argv=None):
                          "does not bin the same way: not supported together")
     if args.rtt >= 1:
         raise SystemExit("--rtt takes a burn-in fraction in [0, 1)")
+    if args.rtt_bf != 0 or args.rtt_bf_lambda != 0:
+        from literate_amd.logs import rtt_bf_arg_error
+        err = rtt_bf_arg_error(args.rtt_bf, args.rtt_bf_lambda, args.rtt)
+        if err:
+            raise SystemExit(err)
     if args.ess != -1.0:
         from literate_amd.logs import ess_arg_error
         err = ess_arg_error(args.ess, args.n, args.s)
@@ -235,7 +250,9 @@ def main(argv=None):
         files = [logs.log_paths(args.d, model, args.out, c)[1]["mcmc"] for c in range(args.chains)]
         logs.combine_logs(files, os.path.dirname(files[0]), args.combine)
     if args.rtt >= 0 and n_samples:
-        write_rtt(args, eng, n_local, world, rank)
+        res = write_rtt(args, eng, n_local, world, rank)
+        if args.rtt_bf > 0 and rank == 0:
+            write_rtt_bf(args, eng, res, rseed)
     if args.ess != -1.0:
         stem = logs.log_paths(args.d, args.model_BDI, args.out)[1]["div"][:-len("_div.log")]
         logs.write_run_ess(eng, n_local, args.chains, world, rank, args.ess, args.s, stem)
@@ -260,13 +277,31 @@ def write_rtt(args, eng, n_local, world, rank):
     local = eng.trace[burn:S][:, :n_local]
     rows = lrd.gather_traces(local.contiguous(), args.chains) if world > 1 else local
     if rank != 0:
-        return
+        return None
     res = ops.rtt_summary(rows, S - burn, eng.start_time, eng.end_time, burnin=0.0, pooled=True)
     out_dir, paths = logs.log_paths(args.d, args.model_BDI, args.out)
     stem = paths["div"][:-len("_div.log")]
     logs.write_rtt_tables(stem, res.time, res.rates[0].cpu().numpy(), res.shift_freq[0].cpu().numpy(),
                           res.k_counts[0].cpu().numpy())
     print("posterior rates through time: %s_RTT.tsv, %s_RTT_K.tsv (%d samples)" % (stem, stem, res.n_samples))
+    return res
+
+
+def write_rtt_bf(args, eng, res, rseed):
+    """--rtt_bf REPS (rank 0, after write_rtt, on its RttSummary): the prior on shift times over the run's time span by
+    Monte Carlo on the GPU (ops.shift_prior, the stream the run's seed names; get_prior_shift of plotRJforward.v3.py), then
+    the Bayes-factor tables (logs.write_rtt_bf_tables).  The thresholds are computed once and serve births and deaths, as
+    the script computes them in its birth call and reuses them."""
+    from literate_amd import logs, ops
+    lam = args.rtt_bf_lambda if args.rtt_bf_lambda > 0 else None
+    prior = ops.shift_prior(eng.start_time, eng.end_time, n_reps=args.rtt_bf, seed=rseed, poi_lambda=lam)
+    stem = logs.log_paths(args.d, args.model_BDI, args.out)[1]["div"][:-len("_div.log")]
+    ps, bf2, bf6 = logs.write_rtt_bf_tables(stem, res.time, res.rates[0].cpu().numpy(), res.shift_freq[0].cpu().numpy(),
+                                            res.k_counts[0].cpu().numpy(), prior.totals.cpu().numpy(),
+                                            prior.shift_hist.cpu().numpy(), prior.k_accepted.cpu().numpy(), args.rtt_bf,
+                                            args.rtt_bf_lambda)
+    print("Bayes factors for rate shifts: %s_RTT_BF.tsv, _RTT_BF_prior.tsv, _RTT_BF_K.tsv (%d prior replicates, prior "
+          "frequency %s, bf2 = %s, bf6 = %s)" % (stem, args.rtt_bf, ps, bf2, bf6))
 
 
 if __name__ == "__main__":

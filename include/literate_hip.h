@@ -231,6 +231,37 @@ int lr_rtt_summary(const double* trace, int32_t n_samples, int32_t n_chains, dou
                    double burnin, int32_t pooled, double* rates, double* shift_freq, int64_t* k_counts,
                    void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- The prior on the times of rate shifts, by Monte Carlo: what the shift frequencies of lr_rtt_summary are read against
+ * (plotRJforward.v3.py get_prior_shift :58-89; calcBF :54-56 and get_r_plot :182-195 turn the result into the 2 ln BF = 2
+ * and = 6 thresholds, literate_amd/shift_bf.py) -----------------------------------------------------------------------------
+ * start_age / end_age = a / b and the bins as lr_rtt_summary: edges np.arange(a, b), n_bins = ceil(b - a) - 1 = int(b - a).
+ * Replicates rep0 .. rep0 + n_reps - 1; replicate i draws from Philox4x32-10 with key ((uint32) seed, (uint32) (seed >> 32))
+ * and counter (i, purpose 40, idx), u_a / u_b as everywhere in this library; every product and sum below is rounded on its
+ * own (no fused multiply-add), so that a numpy restatement gives the same doubles:
+ *   idx 0 (poi_lambda <= 0, the reference's Gamma(2, 1) hyper-prior): p0 = (1 - u_a) (1 - u_b), lambda = -log p0;
+ *         poi_lambda > 0 (a run with a fixed -Poisson_prior): lambda = poi_lambda, p0 = exp(-lambda);
+ *   idx 1: K ~ zero-truncated Poisson(lambda) by inversion: t = p0 + u_a (1 - p0); k = 0, p = cum = p0; repeat { k++;
+ *         p = (p lambda) / k; cum = cum + p } while cum <= t and k < LR_SHIFT_PRIOR_KCAP; K = k.  A replicate the cap stopped
+ *         (cum <= t still holds) counts in totals[2] and goes on as K = LR_SHIFT_PRIOR_KCAP;
+ *   idx 2 + (j >> 1), member a for even j, b for odd j: shift time x_j = (a - 1) + ((b + 1) - (a - 1)) u, j < K - 1.
+ * A replicate is rejected when two of the K + 1 points {a, b, x_j} differ by less than 1 (the rounded fp64 difference:
+ * min(np.diff(np.sort(points))) < 1).  (The reference takes K as the first positive of 1000 Poisson draws and silently
+ * skips the replicate when there is none, probability 1 / 1001^2; here K is always drawn.)  Outputs, exact integers:
+ *   totals [4]: accepted replicates, shift times of accepted replicates that fall in a bin, replicates the cap stopped,
+ *               shift times of accepted replicates (sum of K - 1);
+ *   shift_hist [n_bins]: those shift times per bin (np.histogram on the edges: e_i <= x < e_{i+1}, the last bin closed);
+ *   k_drawn / k_accepted [LR_SHIFT_PRIOR_KCAP]: replicates / accepted replicates with K = 1 .. LR_SHIFT_PRIOR_KCAP.
+ * accumulate = 0: the outputs are zeroed on the stream first; 1: added to (a replicate range sharded over calls).  The
+ * result depends on (a, b, seed, the replicate range, poi_lambda) only: integer atomics, no floating-point ones; at most
+ * LR_SHIFT_PRIOR_BLOCKS workgroups stride over the replicates.  No workspace.
+ * LR_ERR_SIZE: n_bins < 1 or > LR_MAX_BINS or != int(b - a), n_reps < 1 or > 2^40, rep0 < 0, poi_lambda > 700 or NaN.      */
+#define LR_SHIFT_PRIOR_KCAP 64
+#define LR_SHIFT_PRIOR_BLOCKS 768
+int lr_shift_prior(double start_age, double end_age, int64_t rep0, int64_t n_reps, uint64_t seed, double poi_lambda,
+                   int32_t accumulate, int64_t* totals /* [4] */, int64_t* shift_hist /* [n_bins] */,
+                   int64_t* k_drawn /* [LR_SHIFT_PRIOR_KCAP] */, int64_t* k_accepted /* [LR_SHIFT_PRIOR_KCAP] */,
+                   void* stream);
+
 /* ---- Convergence summary: per-chain ESS and split R-hat (the check the reference's tutorial does in Tracer) ------------
  * rows: [n_samples, n_chains, row_width] doubles, row (sample s, chain c) at rows + (s * n_chains + c) * row_width - the
  * engine's trace (its first n_samples slots) or rows a caller assembled.  cols (host): the n_cols column indices to

@@ -16,6 +16,7 @@ LR_STATE_ROWS, LR_ISTATE_ROWS = 9, 5
 LR_TRACE_HEAD = 13
 LR_TRACE_W = LR_TRACE_HEAD + 2 * (2 * LR_KMAX - 1)
 LR_SIMBATCH_GROUPS, LR_SIMBATCH_LDS_SLOTS = 512, 16384      # lr_simulate_bd_batch: most workgroups, list positions in LDS
+LR_SHIFT_PRIOR_KCAP, LR_SHIFT_PRIOR_BLOCKS = 64, 768      # lr_shift_prior: most rates a replicate draws, most workgroups
 LR_ESS_LDS_ROWS = 16384      # lr_ess_summary: longest kept series held in LDS (longer ones stream from the workspace)
 # rows / scalar slots (include/literate_hip.h)
 ROW_L, ROW_M, ROW_TL, ROW_TM, ROW_PL, ROW_PM, ROW_PTL, ROW_PTM, ROW_SCALARS = range(9)
@@ -72,6 +73,7 @@ SIGNATURES = {
     "lr_format_rows": (c_i64, [c_vp, c_vp, c_i64, C.c_uint64, c_i32, c_vp, c_i64]),
     "lr_rtt_summary_workspace_bytes": (c_i64, [c_i32, c_i32, c_f64, c_f64, c_f64, c_i32]),
     "lr_rtt_summary": (c_i32, [c_vp, c_i32, c_i32, c_f64, c_f64, c_f64, c_i32, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "lr_shift_prior": (c_i32, [c_f64, c_f64, c_i64, c_i64, C.c_uint64, c_f64, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "lr_ess_summary_workspace_bytes": (c_i64, [c_i32, c_i32, c_i32, c_vp, c_i32, c_f64, c_i32]),
     "lr_ess_summary": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_i32, c_f64, c_i32, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
     "lr_col_summary_workspace_bytes": (c_i64, [c_i32, c_i32, c_i32, c_vp, c_i32, c_f64, c_i32, c_i32]),

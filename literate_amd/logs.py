@@ -447,6 +447,73 @@ def write_rtt_tables(stem, time, rates, shift_freq, k_counts):
             f.write("%d\t%d\t%d\n" % (k + 1, int(k_counts[0, k]), int(k_counts[1, k])))
 
 
+RTT_BF_HEAD = ["time", "birth_counts", "death_counts", "prior_bin", "birth_2lnBF", "death_2lnBF", "birth_BF2", "birth_BF6",
+               "death_BF2", "death_BF6"]
+RTT_BF_PRIOR_HEAD = ["reps", "accepted", "capped", "poi_lambda", "prior_s", "bf2", "bf6", "birth_2lnBF_shift",
+                     "death_2lnBF_shift"]
+RTT_BF_K_HEAD = ["n_rates", "prior", "post_l", "post_m"]
+
+
+def rtt_bf_arg_error(reps, lam, rtt):
+    """Why a CLI's --rtt_bf REPS [--rtt_bf_lambda L] cannot run (None when it can, or when it is off: REPS = 0)."""
+    if reps == 0 and lam == 0:
+        return None
+    if reps < 0 or reps > 1 << 40:
+        return "--rtt_bf takes a number of prior replicates between 1 and 2^40"
+    if reps == 0:
+        return "--rtt_bf_lambda sets the prior that --rtt_bf REPS simulates: it needs --rtt_bf"
+    if rtt < 0:
+        return "--rtt_bf sets the shift frequencies of --rtt against their prior: it needs --rtt BURNIN"
+    if not (0 <= lam <= 700):
+        return "--rtt_bf_lambda takes the fixed -Poisson_prior of the run, 0 < L <= 700 (0: the Gamma(2, 1) hyper-prior)"
+    return None
+
+
+def write_rtt_bf_tables(stem, time, rates, shift_freq, k_counts, totals, shift_hist, k_accepted, reps, poi_lambda=0.0):
+    """The shift frequencies of write_rtt_tables set against the Monte Carlo prior on shift times (ops.shift_prior's counts
+    totals / shift_hist / k_accepted over `reps` replicates; poi_lambda 0 = the Gamma(2, 1) hyper-prior); host arrays, the
+    first four as write_rtt_tables takes them.  Numbers as str(float), counts as integers.
+    <stem>_RTT_BF.tsv, one line per unit bin in ascending time, the columns RTT_BF_HEAD: the two sampled frequencies, the
+      prior frequency of the bin itself (hist[bin] / accepted), 2 ln BF of each sampled frequency against the reference's
+      bin-mean prior (shift_bf.prior_s), and the birth_BF2 / birth_BF6 / death_BF2 / death_BF6 vectors of get_r_plot
+      (plotRJforward.v3.py :188-195) - the thresholds computed once and used for both, as the script does;
+    <stem>_RTT_BF_prior.tsv, one line, RTT_BF_PRIOR_HEAD: the prior run, prior_s and the thresholds (the script's `bf2 =`,
+      `bf6 =` lines), and 2 ln BF of 'at least one shift' against a constant rate for births and for deaths;
+    <stem>_RTT_BF_K.tsv, one line per number of rates, RTT_BF_K_HEAD: its prior and posterior frequencies."""
+    from . import shift_bf
+    totals = np.asarray(totals, dtype=np.int64)
+    hist = np.asarray(shift_hist, dtype=np.float64)
+    k_acc = np.asarray(k_accepted, dtype=np.float64)
+    accepted = int(totals[0])
+    ps = shift_bf.prior_s(hist, accepted)
+    bf2, bf6 = shift_bf.thresholds(ps)
+    prior_bin = hist / float(accepted) if accepted else np.zeros(len(hist))
+    cols = [np.asarray(time, dtype=float), shift_freq[0], shift_freq[1], prior_bin,
+            shift_bf.two_ln_bf(shift_freq[0], ps), shift_bf.two_ln_bf(shift_freq[1], ps)]
+    for kind in range(2):
+        cols += list(shift_bf.flags(shift_freq[kind], rates[kind, 0], bf2, bf6))
+    with open(stem + "_RTT_BF.tsv", "w") as f:
+        f.write("\t".join(RTT_BF_HEAD) + "\n")
+        for i in range(len(cols[0])):
+            f.write("\t".join(str(float(c[i])) for c in cols) + "\n")
+    with open(stem + "_RTT_BF_prior.tsv", "w") as f:
+        f.write("\t".join(RTT_BF_PRIOR_HEAD) + "\n")
+        vals = [float(poi_lambda), ps, bf2, bf6, shift_bf.k_bayes_factor(k_counts[0], k_acc),
+                shift_bf.k_bayes_factor(k_counts[1], k_acc)]
+        f.write("%d\t%d\t%d\t" % (int(reps), accepted, int(totals[2])) + "\t".join(str(float(v)) for v in vals) + "\n")
+    post = np.zeros((2, len(k_acc)))
+    n_post = np.asarray(k_counts, dtype=np.float64).sum(axis=1)
+    for kind in range(2):
+        if n_post[kind] > 0:
+            post[kind, :k_counts.shape[1]] = np.asarray(k_counts[kind], dtype=np.float64) / n_post[kind]
+    with open(stem + "_RTT_BF_K.tsv", "w") as f:
+        f.write("\t".join(RTT_BF_K_HEAD) + "\n")
+        for k in range(len(k_acc)):
+            pk = k_acc[k] / accepted if accepted else 0.0
+            f.write("%d\t%s\t%s\t%s\n" % (k + 1, str(float(pk)), str(float(post[0, k])), str(float(post[1, k]))))
+    return ps, bf2, bf6
+
+
 ESS_HEAD = ["parameter", "mean", "ess_pooled", "ess_min", "chain_ess_min", "rhat", "chains_ess_below_200", "chains_constant"]
 ESS_CHAIN_HEAD = ["chain", "parameter", "mean", "ess", "act", "se_mean", "stop_lag"]
 

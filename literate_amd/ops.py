@@ -493,6 +493,44 @@ def rtt_summary(trace, n_samples, start_age, end_age, burnin=0.2, pooled=True, w
     return RttSummary(time, rates, freq, kc, per * C if pooled else per)
 
 
+ShiftPrior = namedtuple("ShiftPrior", "totals shift_hist k_drawn k_accepted")
+ShiftPrior.__doc__ = """lr_shift_prior's counts (int64 device tensors).  totals [4]: accepted replicates, their shift times that fall
+in a bin, replicates the cap on K stopped, their shift times in all; shift_hist [n_bins]: the accepted shift times per unit
+bin (the bins of rtt_summary); k_drawn / k_accepted [LR_SHIFT_PRIOR_KCAP]: replicates / accepted replicates with K = 1 ..."""
+
+
+def shift_prior(start_age, end_age, n_reps=1 << 20, seed=0, poi_lambda=None, rep0=0, out=None):
+    """The prior on the times of rate shifts over [start_age, end_age] by Monte Carlo (lr_shift_prior: get_prior_shift of
+    plotRJforward.v3.py) -> ShiftPrior.  Replicates rep0 .. rep0 + n_reps - 1 of the stream `seed` names; poi_lambda None
+    (or <= 0): the reference's Gamma(2, 1) hyper-prior on the Poisson rate, > 0: that fixed rate (a run made with
+    -Poisson_prior).  out: a ShiftPrior of an earlier call over the same span to ADD this range's counts to (a replicate
+    range sharded over calls); it is returned.  literate_amd.shift_bf turns the counts into Bayes-factor thresholds.
+    The default of 2^20 replicates (0.14 ms on an MI355X, 0.1 % of Monte Carlo noise on the prior frequency, a third of
+    the reference's) stays below the cost of a small run's rtt_summary; 2^24 takes 1.6 ms (profiles/EXPERIMENTS.md)."""
+    torch = _torch()
+    lib = _hip.load()
+    a, b = float(start_age), float(end_age)
+    lam = 0.0 if poi_lambda is None else float(poi_lambda)
+    nb = int(np.ceil(b - a)) - 1 if 1.0 < b - a <= _hip.LR_MAX_BINS + 1.0 else 0      # (else the library refuses the span)
+    if out is None:
+        dev = "cuda"
+        # (a span the library refuses still gets a histogram to point at: the refusal is the library's, LR_ERR_SIZE)
+        res = ShiftPrior(torch.empty(4, dtype=torch.int64, device=dev), torch.empty(max(nb, 1), dtype=torch.int64, device=dev),
+                         torch.empty(_hip.LR_SHIFT_PRIOR_KCAP, dtype=torch.int64, device=dev),
+                         torch.empty(_hip.LR_SHIFT_PRIOR_KCAP, dtype=torch.int64, device=dev))
+    else:
+        res = out
+        sizes = (4, nb, _hip.LR_SHIFT_PRIOR_KCAP, _hip.LR_SHIFT_PRIOR_KCAP)
+        if any(t.dtype != torch.int64 or t.numel() != n or not t.is_contiguous() or not t.is_cuda for t, n in zip(res, sizes)):
+            raise ValueError("out must be the ShiftPrior of a call over the same span")
+    dev = res.totals.device
+    rc = _hip.launch(lib.lr_shift_prior, dev, a, b, int(rep0), int(n_reps), int(seed) & 0xFFFFFFFFFFFFFFFF, lam,
+                     int(out is not None), _hip.ptr(res.totals), _hip.ptr(res.shift_hist), _hip.ptr(res.k_drawn),
+                     _hip.ptr(res.k_accepted))
+    _hip.check(rc, "lr_shift_prior")
+    return res
+
+
 EssSummary = namedtuple("EssSummary", "mean ess act se_mean stop_lag pooled_mean pooled_ess rhat n")
 EssSummary.__doc__ = """lr_ess_summary's results.  mean, ess, act (in samples), se_mean float64 and stop_lag int32: [C, K] per chain and
 column; pooled_mean, pooled_ess, rhat: [K]; n: rows kept per chain.  ESS and ACT are NaN, SE 0 and the stop lag 0 where a
