@@ -34,6 +34,15 @@ def build_parser():
                    '<stem>_summary_params.tsv (mean and HPD of the logged parameters) beside the logs, all chains pooled '
                    'after this burn-in fraction is dropped from each; computed on the GPU from the resident trace '
                    '(extension)')
+    p.add_argument('--ppc', type=float, default=-1.0, help='after the run, write <stem>_PPC.tsv and <stem>_PPC_fit.tsv beside '
+                   'the logs: a posterior predictive check that simulates lineages forward under --ppc_draws posterior '
+                   'draws of the parameters (this burn-in fraction dropped per chain), the rates of every simulated step recomputed from the diversity living at that step, and sets the predicted births, '
+                   'deaths and diversity per bin beside the observed ones; simulated on the GPU; not with -rm_first_bin 1 '
+                   '(extension)')
+    p.add_argument('--ppc_draws', type=int, default=1000, help='posterior draws the check simulates under')
+    p.add_argument('--ppc_scale', type=int, default=100, help='simulation steps per time unit (the reference Simulator.scale)')
+    p.add_argument('--ppc_start_bin', type=int, default=-1, help='bin at whose left edge the free-running simulations start '
+                   '(default: the first bin after bin 0 that starts with an observed lineage)')
     p.add_argument('--block', type=int, default=0, help='iterations per device window (logs are flushed once per window; '
                    'default: -p rounded up to ~50000)')
     return p
@@ -49,6 +58,11 @@ def main(argv=None):
     if args.summary != -1.0:
         from literate_amd.logs import summary_arg_error
         err = summary_arg_error(args.summary, args.n, args.s, args.chains)
+        if err:
+            raise SystemExit(err)
+    if args.ppc != -1.0:
+        from literate_amd.ppc import dd_arg_error
+        err = dd_arg_error(args.ppc, args.rm_first_bin, args.ppc_draws, args.ppc_scale)
         if err:
             raise SystemExit(err)
     import torch
@@ -119,6 +133,10 @@ def main(argv=None):
     if args.summary != -1.0:
         from literate_amd.logs import write_run_summary
         write_run_summary(eng, n_local, args.chains, world, rank, args.summary, stem)
+    if args.ppc != -1.0 and n_samples:
+        from literate_amd.ppc import write_run_ppc_dd
+        write_run_ppc_dd(eng, n_local, args.chains, world, rank, args.ppc, args.ppc_draws, args.ppc_scale, seed, stem,
+                         start_bin=args.ppc_start_bin if args.ppc_start_bin >= 0 else None)
     eng.close()
     if world > 1:
         dist.barrier()

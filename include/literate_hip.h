@@ -197,6 +197,30 @@ int lr_simulate_bd_batch(const double* lam_bins /* [n_reps, n_bins] */, const do
                          int64_t* counts /* [n_reps, 4, n_bins] */, int64_t* totals /* [n_reps, 4] */,
                          void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- Batched diversity-dependent simulator: lr_simulate_bd_batch's replicate under DDRate's rate map (the replicates of
+ * DDRate.py's posterior predictive check).  Replicate r is lr_simulate_bd_batch's replicate with ONE change: the thresholds
+ * of step t are recomputed from the count n_t living at the start of that step,
+ *   (br, dr) = the DDRate rates (DD:71-100, csrc/lr_dd.h lr_dd_bin_rates: the function lr_dd_rates and the engine evaluate)
+ *              of params[r] = [l_max, k, x0, div_0, L, m_max, nuB, nuD] as the trace holds them (x0 and L unshifted), at
+ *              x = x_bins[r, t / steps_per_bin] (the TIME_RANGE value of the simulated bin) with (double) n_t in the place of
+ *              DT[b]; the 1e-15 floor and x ** nu = exp(nu * lr_log x) as there;
+ *   lt = br / (double) steps_per_bin, mt = dr / (double) steps_per_bin.
+ * The living count stands in for DT[b]: the model's DT[b] is the lineage-time lived in bin b, unknown until the bin is
+ * over, and the reference's own simulators (simulateRateABC.v2.py:142-166, notebook 4's
+ * Diversity_Dependence_Rate_Generator) feed back the count living at the step.  The draws - key ((uint32) (seed + r),
+ * lineage slot), counter (t, 24, 0) - and the comparisons - u < lt births, otherwise !(u < lt + mt) survives - are
+ * lr_simulate_bd_batch's, so a nan rate means "no event"; counts, totals, capacity, n_start, the workspace and its size
+ * have that function's layout and meaning, and with m_birth = 0, m_death = 0 the results equal its results on the
+ * constant rates l_max, m_max bit for bit.  m_birth 0..2, m_death -2..2 as lr_dd_rates; anything else is LR_ERR_MODEL.
+ * LR_ERR_NULL / LR_ERR_SIZE / LR_ERR_WORKSPACE as lr_simulate_bd_batch; every error is returned before any launch.     */
+int64_t lr_simulate_dd_batch_workspace_bytes(int32_t n_reps, int32_t n_bins, int32_t steps_per_bin, int64_t capacity);
+int lr_simulate_dd_batch(const double* params /* [n_reps, 8]: l_max, k, x0, div_0, L, m_max, nuB, nuD, as the trace holds them */,
+                         const double* x_bins /* [n_reps, n_bins]: TIME_RANGE value of each simulated bin */,
+                         int32_t m_birth, int32_t m_death, int32_t n_reps, int32_t n_bins, int32_t steps_per_bin,
+                         const int64_t* n_start, int64_t capacity, uint64_t seed,
+                         int64_t* counts /* [n_reps, 4, n_bins] */, int64_t* totals /* [n_reps, 4] */,
+                         void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- the text form of the logs (host only, no GPU) ---------------------------------
  * The reference writes every number through Python's csv module (LRF:334-359, DD:236-238): str(float), the shortest
  * decimal string that reads back to the same double, "24.0" / "1e-05" / "1.5e+16" by Python's rules.  lr_format_rows

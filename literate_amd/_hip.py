@@ -69,6 +69,9 @@ SIGNATURES = {
     "lr_simulate_bd_batch_workspace_bytes": (c_i64, [c_i32, c_i32, c_i32, c_i64]),
     "lr_simulate_bd_batch": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_i64, C.c_uint64, c_vp, c_vp, c_vp, c_i64,
                                    c_vp]),
+    "lr_simulate_dd_batch_workspace_bytes": (c_i64, [c_i32, c_i32, c_i32, c_i64]),
+    "lr_simulate_dd_batch": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_i64, C.c_uint64, c_vp, c_vp, c_vp,
+                                   c_i64, c_vp]),
     "lr_trend_rates": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "lr_format_rows": (c_i64, [c_vp, c_vp, c_i64, C.c_uint64, c_i32, c_vp, c_i64]),
     "lr_rtt_summary_workspace_bytes": (c_i64, [c_i32, c_i32, c_f64, c_f64, c_f64, c_i32]),

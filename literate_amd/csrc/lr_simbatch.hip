@@ -16,10 +16,20 @@
 // workgroup's slice of the workspace beyond: a list that outgrows LDS in mid-run just continues there, and the
 // result does not depend on where a position lived.  Per-bin counters are registers, stored once per bin by one
 // thread with ordinary stores.  No floating-point atomics; the only atomic is the integer ticket.
+//
+// Where the two thresholds of a step come from is a parameter of the walk (SRC below), and there are two sources.
+// lr_sb_fixed (lr_simulate_bd_batch): per-bin rates given before the launch, one division per bin.  lr_sb_dd
+// (lr_simulate_dd_batch): DDRate's diversity-dependent rates, recomputed at EVERY step from the count n_t living at its
+// start by lr_dd_bin_rates of lr_dd.h - the function the engine and lr_dd_rates use, with n_t in the place of DT[b].  The
+// model's DT[b] is the lineage-time lived in bin b, which is not known until the bin is over; the reference's own
+// simulators (simulateRateABC.v2.py:142-166, notebook 4's Diversity_Dependence_Rate_Generator) feed back the count living
+// at the step, and so does this one.  n_t is the same value in every thread, so every thread evaluates the map itself
+// (one lr_log, two exp per step): nothing is broadcast, and the parameters of the replicate sit in scalar registers.
 #include <hip/hip_runtime.h>
 
 #include "../../include/literate_hip.h"
 #include "lr_device.h"
+#include "lr_dd.h"
 
 #define LR_P_SIM 24
 #define LR_SB_THREADS 512
@@ -39,9 +49,62 @@ static inline long long lr_sb_slice_slots(long long capacity) {
     return (over + 63) / 64 * 64;
 }
 
-struct lr_sb_args {
+// The threshold sources.  A source makes a per-replicate object with bin(b, spb), called by every thread when bin b
+// begins, and step(n, spb, &lt, &ltmt), called at every step with the living count: the birth threshold lt and the
+// death threshold lt + mt.
+struct lr_sb_fixed {
     const double* lam_bins;
     const double* mu_bins;
+    struct rep {
+        const double* lam;
+        const double* mu;
+        double lt, ltmt;
+        __device__ __forceinline__ void bin(int b, int spb) {
+            lt = lam[b] / (double)spb;
+            const double mt = mu[b] / (double)spb;
+            ltmt = lt + mt;
+        }
+        __device__ __forceinline__ void step(long long, int, double* lt_, double* ltmt_) const { *lt_ = lt, *ltmt_ = ltmt; }
+    };
+    __device__ __forceinline__ rep replicate(int r, int nb) const {
+        return rep{lam_bins + (long long)r * nb, mu_bins + (long long)r * nb, 0.0, 0.0};
+    }
+};
+
+struct lr_sb_dd {
+    const double* params;                   // [n_reps, LR_DD_NPAR]
+    const double* x_bins;                   // [n_reps, n_bins]
+    int m_birth, m_death;
+    struct rep {
+        lr_dd_params p;
+        const double* xs;
+        double x;
+        int m_birth, m_death;
+        __device__ __forceinline__ void bin(int b, int) { x = xs[b]; }
+        __device__ __forceinline__ void step(long long n, int spb, double* lt_, double* ltmt_) const {
+            double br, dr, niche, frac;
+            lr_dd_bin_rates(p, x, (double)n, m_birth, m_death, &br, &dr, &niche, &frac);
+            const double lt = br / (double)spb, mt = dr / (double)spb;
+            *lt_ = lt, *ltmt_ = lt + mt;
+        }
+    };
+    __device__ __forceinline__ rep replicate(int r, int nb) const {
+        // r is the same in every thread of the block: say so, and the eight parameters are scalar loads
+        const int ru = __builtin_amdgcn_readfirstlane(r);
+        const double* a = params + (long long)ru * LR_DD_NPAR;
+        rep q;
+        q.p.l_max = a[0], q.p.k = a[1], q.p.x0 = a[2], q.p.div_0 = a[3];
+        q.p.L = a[4], q.p.m_max = a[5], q.p.nuB = a[6], q.p.nuD = a[7];
+        q.xs = x_bins + (long long)ru * nb, q.x = 0.0;
+        q.m_birth = m_birth, q.m_death = m_death;
+        return q;
+    }
+};
+
+// the kernel argument: the threshold source first, then what every source shares
+template <class SRC>
+struct lr_sb_args {
+    SRC src;
     const long long* n_start;
     long long* counts;
     long long* totals;
@@ -62,7 +125,8 @@ __device__ __forceinline__ void lr_sb_put(unsigned int* s_list, unsigned int* g_
 }
 
 // One replicate.  n, created and the per-bin sums hold the same value in every thread (they come from block totals).
-__device__ void lr_sb_run(const lr_sb_args& a, int r, unsigned int* s_list, unsigned int* g_list, int (*s_wtot)[LR_SB_WAVES],
+template <class SRC>
+__device__ void lr_sb_run(const lr_sb_args<SRC>& a, int r, unsigned int* s_list, unsigned int* g_list, int (*s_wtot)[LR_SB_WAVES],
                           int& parity) {
     const int tid = threadIdx.x, lane = tid & (LR_WAVE - 1), wave = tid / LR_WAVE;
     const int L = a.lds_slots, nb = a.n_bins, spb = a.steps_per_bin;
@@ -75,8 +139,7 @@ __device__ void lr_sb_run(const lr_sb_args& a, int r, unsigned int* s_list, unsi
     for (long long p = tid; p < n0; p += LR_SB_THREADS) lr_sb_put(s_list, g_list, L, p, (unsigned int)p);
     __syncthreads();
     const uint32_t key = (uint32_t)(a.seed + (unsigned long long)r);
-    const double* lam = a.lam_bins + (long long)r * nb;
-    const double* mu = a.mu_bins + (long long)r * nb;
+    typename SRC::rep rates = a.src.replicate(r, nb);
     long long* cnt = a.counts + 4ll * r * nb;
     long long n = n0, created = n0, first_empty = -1;
     int overflow = 0;
@@ -85,8 +148,7 @@ __device__ void lr_sb_run(const lr_sb_args& a, int r, unsigned int* s_list, unsi
             if (first_empty < 0) first_empty = (long long)b * spb;
             break;
         }
-        const double lt = lam[b] / (double)spb, mt = mu[b] / (double)spb;
-        const double ltmt = lt + mt;
+        rates.bin(b, spb);
         const long long at_start = n;
         long long births_b = 0, deaths_b = 0, steps_b = 0;
         for (int s = 0; s < spb; ++s) {
@@ -95,6 +157,8 @@ __device__ void lr_sb_run(const lr_sb_args& a, int r, unsigned int* s_list, unsi
                 if (first_empty < 0) first_empty = t;
                 break;
             }
+            double lt, ltmt;                // the thresholds of this step
+            rates.step(n, spb, &lt, &ltmt);
             steps_b += n;
             long long w = 0;                // survivors written so far
             int born = 0;                   // births of this step
@@ -150,7 +214,8 @@ __device__ void lr_sb_run(const lr_sb_args& a, int r, unsigned int* s_list, unsi
     if (tid == 0) tot[0] = created, tot[1] = overflow ? 0 : n, tot[2] = overflow, tot[3] = first_empty;
 }
 
-__global__ __launch_bounds__(LR_SB_THREADS) void lr_simbatch_kernel(lr_sb_args a) {
+template <class SRC>
+__device__ __forceinline__ void lr_sb_block(const lr_sb_args<SRC>& a) {
     extern __shared__ unsigned int s_list[];
     __shared__ int s_wtot[2][LR_SB_WAVES];
     __shared__ int s_next;
@@ -171,6 +236,9 @@ __global__ __launch_bounds__(LR_SB_THREADS) void lr_simbatch_kernel(lr_sb_args a
     }
 }
 
+__global__ __launch_bounds__(LR_SB_THREADS) void lr_simbatch_kernel(lr_sb_args<lr_sb_fixed> a) { lr_sb_block(a); }
+__global__ __launch_bounds__(LR_SB_THREADS) void lr_simbatch_dd_kernel(lr_sb_args<lr_sb_dd> a) { lr_sb_block(a); }
+
 static int lr_sb_check_sizes(int32_t n_reps, int32_t n_bins, int32_t steps_per_bin, int64_t capacity) {
     if (n_reps < 1 || n_bins < 1 || steps_per_bin < 1 || n_bins > LR_MAX_BINS) return LR_ERR_SIZE;
     if (capacity < 1 || capacity > LR_SB_MAX_CAPACITY) return LR_ERR_SIZE;
@@ -186,18 +254,17 @@ extern "C" int64_t lr_simulate_bd_batch_workspace_bytes(int32_t n_reps, int32_t 
     return LR_SB_HEAD + groups * lr_sb_slice_slots(capacity) * 4;
 }
 
-extern "C" int lr_simulate_bd_batch(const double* lam_bins, const double* mu_bins, int32_t n_reps, int32_t n_bins,
-                                    int32_t steps_per_bin, const int64_t* n_start, int64_t capacity, uint64_t seed,
-                                    int64_t* counts, int64_t* totals, void* workspace, int64_t workspace_bytes,
-                                    void* stream_) {
-    if (!lam_bins || !mu_bins || !n_start || !counts || !totals || !workspace) return LR_ERR_NULL;
-    const int rc = lr_sb_check_sizes(n_reps, n_bins, steps_per_bin, capacity);
-    if (rc != LR_OK) return rc;
+// the checks that do not depend on the threshold source, then the two memsets and the launch
+template <class SRC, class KERNEL>
+static int lr_sb_launch(KERNEL kernel, const SRC& src, int32_t n_reps, int32_t n_bins, int32_t steps_per_bin,
+                        const int64_t* n_start, int64_t capacity, uint64_t seed, int64_t* counts, int64_t* totals,
+                        void* workspace, int64_t workspace_bytes, void* stream_) {
     if (workspace_bytes < lr_simulate_bd_batch_workspace_bytes(n_reps, n_bins, steps_per_bin, capacity))
         return LR_ERR_WORKSPACE;
     hipStream_t stream = (hipStream_t)stream_;
-    lr_sb_args a;
-    a.lam_bins = lam_bins, a.mu_bins = mu_bins, a.n_start = (const long long*)n_start;
+    lr_sb_args<SRC> a;
+    a.src = src;
+    a.n_start = (const long long*)n_start;
     a.counts = (long long*)counts, a.totals = (long long*)totals;
     a.ticket = (unsigned int*)workspace;
     a.slices = (unsigned int*)((char*)workspace + LR_SB_HEAD);
@@ -212,6 +279,34 @@ extern "C" int lr_simulate_bd_batch(const double* lam_bins, const double* mu_bin
     // (LR_SIMBATCH_LDS_SLOTS * 4 = 64 KiB: two workgroups per CU, and no attribute to raise)
     const size_t lds_bytes = (size_t)a.lds_slots * 4;
     const int groups = n_reps < LR_SIMBATCH_GROUPS ? n_reps : LR_SIMBATCH_GROUPS;
-    hipLaunchKernelGGL(lr_simbatch_kernel, dim3((unsigned)groups), dim3(LR_SB_THREADS), lds_bytes, stream, a);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)groups), dim3(LR_SB_THREADS), lds_bytes, stream, a);
     return (int)hipGetLastError();
+}
+
+extern "C" int lr_simulate_bd_batch(const double* lam_bins, const double* mu_bins, int32_t n_reps, int32_t n_bins,
+                                    int32_t steps_per_bin, const int64_t* n_start, int64_t capacity, uint64_t seed,
+                                    int64_t* counts, int64_t* totals, void* workspace, int64_t workspace_bytes,
+                                    void* stream_) {
+    if (!lam_bins || !mu_bins || !n_start || !counts || !totals || !workspace) return LR_ERR_NULL;
+    const int rc = lr_sb_check_sizes(n_reps, n_bins, steps_per_bin, capacity);
+    if (rc != LR_OK) return rc;
+    return lr_sb_launch(lr_simbatch_kernel, lr_sb_fixed{lam_bins, mu_bins}, n_reps, n_bins, steps_per_bin, n_start, capacity,
+                        seed, counts, totals, workspace, workspace_bytes, stream_);
+}
+
+extern "C" int64_t lr_simulate_dd_batch_workspace_bytes(int32_t n_reps, int32_t n_bins, int32_t steps_per_bin,
+                                                        int64_t capacity) {
+    return lr_simulate_bd_batch_workspace_bytes(n_reps, n_bins, steps_per_bin, capacity);
+}
+
+extern "C" int lr_simulate_dd_batch(const double* params, const double* x_bins, int32_t m_birth, int32_t m_death,
+                                    int32_t n_reps, int32_t n_bins, int32_t steps_per_bin, const int64_t* n_start,
+                                    int64_t capacity, uint64_t seed, int64_t* counts, int64_t* totals, void* workspace,
+                                    int64_t workspace_bytes, void* stream_) {
+    if (!params || !x_bins || !n_start || !counts || !totals || !workspace) return LR_ERR_NULL;
+    const int rc = lr_sb_check_sizes(n_reps, n_bins, steps_per_bin, capacity);
+    if (rc != LR_OK) return rc;
+    if (m_birth < 0 || m_birth > 2 || m_death < -2 || m_death > 2) return LR_ERR_MODEL;      // lr_curve_setup's ranges
+    return lr_sb_launch(lr_simbatch_dd_kernel, lr_sb_dd{params, x_bins, m_birth, m_death}, n_reps, n_bins, steps_per_bin,
+                        n_start, capacity, seed, counts, totals, workspace, workspace_bytes, stream_);
 }

@@ -438,6 +438,50 @@ def simulate_bd_batch(lam_bins, mu_bins, steps_per_bin, n_start, seed, capacity=
     return counts, totals
 
 
+def simulate_dd_batch(params, x_bins, steps_per_bin, n_start, seed, m_birth=2, m_death=2, capacity=None, device=None):
+    """Many independent diversity-dependent simulations in one launch (lr_simulate_dd_batch): simulate_bd_batch's
+    replicate with the thresholds of every step recomputed from the count living at its start by DDRate's rate map
+    (dd_rates' expressions with that count in the place of DT).  params [n_reps, 8]: l_max, k, x0, div_0, L, m_max, nuB,
+    nuD as the trace holds them; x_bins [n_bins] (shared by all replicates) or [n_reps, n_bins]: the TIME_RANGE value of
+    each simulated bin; n_start: an int or [n_reps].  Returns (counts, totals) and takes capacity as simulate_bd_batch."""
+    torch = _torch()
+    lib = _hip.load()
+    par = _dev(params, torch.float64, device)
+    dev = par.device
+    if par.dim() == 1:
+        par = par[None, :]
+    if par.dim() != 2 or par.shape[1] != 8:
+        raise ValueError("params must be [n_reps, 8]")
+    R = int(par.shape[0])
+    x = _dev(x_bins, torch.float64, dev)
+    if x.dim() == 1:
+        x = x[None, :].expand(R, -1)
+    if x.dim() != 2 or x.shape[0] != R:
+        raise ValueError("x_bins must be [n_bins] or [n_reps, n_bins]")
+    x = x.contiguous()
+    nb = int(x.shape[1])
+    if isinstance(n_start, (int, np.integer)):
+        most = int(n_start)
+        n0 = torch.full((R,), most, dtype=torch.int64, device=dev)
+    else:
+        n0 = _dev(n_start, torch.int64, dev).reshape(-1)
+        if n0.numel() != R:
+            raise ValueError("n_start must be an int or hold one entry per replicate")
+        most = int(n0.max()) if capacity is None and R else 0
+    capacity = int(capacity or max(64 * most, 1 << 20))
+    nbytes = lib.lr_simulate_dd_batch_workspace_bytes(R, nb, int(steps_per_bin), capacity)
+    if nbytes < 0:
+        _hip.check(int(nbytes), "lr_simulate_dd_batch_workspace_bytes")
+    counts = torch.empty((R, 4, nb), dtype=torch.int64, device=dev)
+    totals = torch.empty((R, 4), dtype=torch.int64, device=dev)
+    ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
+    rc = _hip.launch(lib.lr_simulate_dd_batch, dev, _hip.ptr(par), _hip.ptr(x), int(m_birth), int(m_death), R, nb,
+                     int(steps_per_bin), _hip.ptr(n0), capacity, int(seed) & 0xFFFFFFFFFFFFFFFF, _hip.ptr(counts),
+                     _hip.ptr(totals), _hip.ptr(ws), ws.numel())
+    _hip.check(rc, "lr_simulate_dd_batch")
+    return counts, totals
+
+
 RttSummary = namedtuple("RttSummary", "time rates shift_freq k_counts n_samples")
 RttSummary.__doc__ = """lr_rtt_summary's results.  time [n_bins] (host): bin centres in ascending time; rates [G, 3, 3, n_bins]:
 (birth, death, net) x (mean, HPD low, HPD high); shift_freq [G, 2, n_bins]; k_counts int64 [G, 2, LR_KMAX] (K = 1 ..

@@ -27,7 +27,12 @@ data show.  Everything stays on the device until the small result tables.
 Time mapping: a bin's simulated births / deaths are the events during its steps - what sp_events / ex_events count on
 year-resolution input (ts = y, te = y + death_jitter).  Branch length is deliberately not compared: on such data the
 observed br_length carries the jitter convention (a full year in the birth bin, death_jitter in the death bin), the
-simulated one does not; diversity at bin edges and event counts have no such ambiguity."""
+simulated one does not; diversity at bin edges and event counts have no such ambiguity.
+
+The other two samplers.  trend_rate.py's rates are fixed per bin (the covariate is data): posterior_predictive_rates is the
+same check started at step 2 from per-bin rates given directly.  DDRate.py's rates are a function of the diversity itself,
+and the check must keep that feedback: posterior_predictive_dd runs both sets through ops.simulate_dd_batch, which
+recomputes the rates of every step from the count living at that step."""
 from collections import namedtuple
 
 import numpy as np
@@ -127,29 +132,20 @@ def draw_rates(flat_rows, idx, n_bins):
     return out[0], out[1]
 
 
-def posterior_predictive(rows, sp_events, ex_events, n_draws, steps_per_bin, seed, start_bin=None, capacity=None,
-                         start_time=0.0):
-    """The check described in the module docstring on post-burn-in trace rows [S', C, LR_TRACE_W] -> PpcResult.
-    start_time: the time of the left edge of bin 0 (only labels the table's rows)."""
-    from . import ops
+def _check(R, sp, ex, spb, seed, free_sim, step_sim, start_bin, capacity, start_time):
+    """Steps 2 - 4 around two simulator calls -> (div_obs, b0, cap, free, step, table, fit).  free_sim(b0, n_start, seed, cap)
+    runs R replicates over bins b0 .. n_bins - 1; step_sim(b0, n1, seed, cap) runs the (n_bins - b0) * R one-bin replicates
+    from n1 (device, replicate (b - b0) * R + i); both return (counts, totals) on the device."""
     import torch
-    if rows.dim() != 3 or rows.shape[2] != LR_TRACE_W:
-        raise ValueError("rows must be [samples, chains, LR_TRACE_W]")
-    sp, ex = np.asarray(sp_events, dtype=np.int64), np.asarray(ex_events, dtype=np.int64)
     n_bins = len(sp)
     div_obs = observed_diversity(sp, ex)
     b0 = pick_start_bin(div_obs, start_bin)
-    flat = rows.reshape(-1, LR_TRACE_W)
-    idx = draw_indices(flat.shape[0], n_draws)
-    R = len(idx)
     cap = int(capacity) if capacity else default_capacity(sp)
-    spb, seed = int(steps_per_bin), int(seed)
-    lam, mu = draw_rates(flat, idx, n_bins)
-    dev = lam.device
     nf = n_bins - b0                                                    # bins simulated
 
     # free-running
-    fc, ft = ops.simulate_bd_batch(lam[:, b0:], mu[:, b0:], spb, int(div_obs[b0]), seed, capacity=cap, device=dev)
+    fc, ft = free_sim(b0, int(div_obs[b0]), seed, cap)
+    dev = fc.device
     keep_f = ft[:, 2] == 0
     n_f = int(keep_f.sum())
     if int(round(0.95 * n_f)) < 2:
@@ -161,10 +157,8 @@ def posterior_predictive(rows, sp_events, ex_events, n_draws, steps_per_bin, see
 
     # one step ahead: replicate (b - b0) * R + i
     real = div_obs[b0:n_bins] >= 1
-    lam1 = lam[:, b0:].t().reshape(-1, 1).contiguous()
-    mu1 = mu[:, b0:].t().reshape(-1, 1).contiguous()
     n1 = torch.as_tensor(np.repeat(div_obs[b0:n_bins], R), device=dev)
-    sc, st = ops.simulate_bd_batch(lam1, mu1, spb, n1, seed + R, capacity=cap, device=dev)
+    sc, st = step_sim(b0, n1, seed + R, cap)
     sc, st = sc.reshape(nf, R, 4), st.reshape(nf, R, 4)
     real_d = torch.as_tensor(real, device=dev)
     keep_s = ~((st[:, :, 2] != 0) & real_d[:, None]).any(0)
@@ -190,9 +184,116 @@ def posterior_predictive(rows, sp_events, ex_events, n_draws, steps_per_bin, see
     fit["coverage_sp_events"], fit["coverage_ex_events"] = coverage(table[:, 1:6]), coverage(table[:, 6:11])
     fit["coverage_diversity"] = coverage(table[:, 11:16])
     host = lambda t: t.cpu().numpy()
-    return PpcResult(idx, host(lam), host(mu), div_obs, b0, int(div_obs[b0]), cap, (seed, seed + R),
-                     dict(counts=host(fc), totals=host(ft), kept=host(keep_f)),
-                     dict(counts=host(sc), totals=host(st), kept=host(keep_s), simulated=real), table, fit)
+    return (div_obs, b0, cap, dict(counts=host(fc), totals=host(ft), kept=host(keep_f)),
+            dict(counts=host(sc), totals=host(st), kept=host(keep_s), simulated=real), table, fit)
+
+
+def posterior_predictive_rates(lam_bins, mu_bins, sp_events, ex_events, steps_per_bin, seed, start_bin=None, capacity=None,
+                               start_time=0.0, draw_rows=None):
+    """Steps 2 - 5 of the module docstring on per-bin rates given directly: lam_bins, mu_bins [R, n_bins], one row per
+    draw (what trend_rate.py's check passes: ops.trend_rates of the drawn rows) -> PpcResult.  draw_rows: the trace rows
+    the draws came from, for the result (default 0 .. R - 1)."""
+    from . import ops
+    import torch
+    sp, ex = np.asarray(sp_events, dtype=np.int64), np.asarray(ex_events, dtype=np.int64)
+    shape = tuple(np.shape(lam_bins))
+    if len(shape) != 2 or tuple(np.shape(mu_bins)) != shape or shape[1] != len(sp) or len(ex) != len(sp):
+        raise ValueError("lam_bins and mu_bins must both be [draws, n_bins], with one bin per entry of sp_events / ex_events")
+    if shape[0] < 1:
+        raise ValueError("posterior predictive check: no draws")
+    pick_start_bin(observed_diversity(sp, ex), start_bin)               # (refused before anything is launched)
+    lam = ops._dev(lam_bins, torch.float64)
+    mu = ops._dev(mu_bins, torch.float64, lam.device)
+    R, dev = int(lam.shape[0]), lam.device
+    spb, seed = int(steps_per_bin), int(seed)
+
+    def free_sim(b0, n_start, seed_, cap):
+        return ops.simulate_bd_batch(lam[:, b0:], mu[:, b0:], spb, n_start, seed_, capacity=cap, device=dev)
+
+    def step_sim(b0, n1, seed_, cap):
+        lam1 = lam[:, b0:].t().reshape(-1, 1).contiguous()
+        mu1 = mu[:, b0:].t().reshape(-1, 1).contiguous()
+        return ops.simulate_bd_batch(lam1, mu1, spb, n1, seed_, capacity=cap, device=dev)
+
+    div_obs, b0, cap, free, step, table, fit = _check(R, sp, ex, spb, seed, free_sim, step_sim, start_bin, capacity, start_time)
+    idx = np.arange(R, dtype=np.int64) if draw_rows is None else np.asarray(draw_rows, dtype=np.int64)
+    return PpcResult(idx, lam.cpu().numpy(), mu.cpu().numpy(), div_obs, b0, int(div_obs[b0]), cap, (seed, seed + R), free,
+                     step, table, fit)
+
+
+def posterior_predictive(rows, sp_events, ex_events, n_draws, steps_per_bin, seed, start_bin=None, capacity=None,
+                         start_time=0.0):
+    """The check described in the module docstring on post-burn-in trace rows [S', C, LR_TRACE_W] -> PpcResult.
+    start_time: the time of the left edge of bin 0 (only labels the table's rows)."""
+    if rows.dim() != 3 or rows.shape[2] != LR_TRACE_W:
+        raise ValueError("rows must be [samples, chains, LR_TRACE_W]")
+    sp = np.asarray(sp_events, dtype=np.int64)
+    div_obs = observed_diversity(sp, ex_events)
+    pick_start_bin(div_obs, start_bin)                                  # (refused before anything is launched)
+    flat = rows.reshape(-1, LR_TRACE_W)
+    idx = draw_indices(flat.shape[0], n_draws)
+    lam, mu = draw_rates(flat, idx, len(sp))
+    return posterior_predictive_rates(lam, mu, sp, ex_events, steps_per_bin, seed, start_bin, capacity, start_time,
+                                      draw_rows=idx)
+
+
+def dd_arg_error(burnin, rm_first_bin, n_draws=1, steps_per_bin=1):
+    """Why DDRate.py's / trend_rate.py's --ppc BURNIN cannot run (None when it can)."""
+    if not (0.0 <= burnin < 1.0):
+        return "--ppc takes a burn-in fraction in [0, 1)"
+    if rm_first_bin:
+        return ("--ppc starts its simulations from the observed diversity, counted up from the first bin; under "
+                "-rm_first_bin 1 the lineages born in the removed bin are missing from that count: not supported together")
+    if n_draws < 1 or steps_per_bin < 1:
+        return "--ppc_draws and --ppc_scale must be at least 1"
+    return None
+
+
+def posterior_predictive_dd(rows, sp_events, ex_events, DT, time_range, m_birth, m_death, n_draws, steps_per_bin, seed,
+                            start_bin=None, capacity=None, start_time=0.0):
+    """DDRate.py's check: steps 1 - 5 of the module docstring with the diversity-dependent simulator
+    (ops.simulate_dd_batch) in both sets of replicates -> PpcResult.  rows: post-burn-in trace rows [S', C, LR_TRACE_W]
+    of a DDRate engine; a draw's parameters are its columns 4:12 (l_max, k, x0, div_0, L, m_max, nuB, nuD).  The rates of
+    every simulated step follow the count living at that step, in the place the model gives to DT[b] (the lineage-time
+    lived in bin b is not known before the bin is over; the reference's simulators feed back the count too):
+    free-running - draw i runs from div_obs[b0] with x = time_range[b0:] (seed + i);
+    one step ahead - replicate (b - b0) * R + i is ONE bin from div_obs[b] with x = time_range[b] (seed + R + that
+    index): the feedback acts inside the bin.
+    lam_bins / mu_bins of the result are ops.dd_rates of the draws at the OBSERVED DT (the log's l_i / m_i columns), for
+    the reader: they do not enter the simulation."""
+    from . import ops
+    import torch
+    if rows.dim() != 3 or rows.shape[2] != LR_TRACE_W:
+        raise ValueError("rows must be [samples, chains, LR_TRACE_W]")
+    sp, ex = np.asarray(sp_events, dtype=np.int64), np.asarray(ex_events, dtype=np.int64)
+    n_bins = len(sp)
+    DT, x = np.asarray(DT, dtype=np.float64), np.asarray(time_range, dtype=np.float64)
+    if len(ex) != n_bins or len(DT) != n_bins or len(x) != n_bins:
+        raise ValueError("sp_events, ex_events, DT and time_range must hold one entry per bin")
+    div_obs = observed_diversity(sp, ex)
+    pick_start_bin(div_obs, start_bin)                                  # (refused before anything is launched)
+    flat = rows.reshape(-1, LR_TRACE_W)
+    idx = draw_indices(flat.shape[0], n_draws)
+    R = len(idx)
+    par = flat[torch.as_tensor(idx, device=flat.device)][:, 4:12].contiguous()
+    dev = par.device
+    spb, seed, mb, md = int(steps_per_bin), int(seed), int(m_birth), int(m_death)
+    # (lr_dd_rates takes at most 65535 parameter vectors a launch)
+    parts = [ops.dd_rates(par[a:a + 65535], DT, mb, md)[:2] for a in range(0, R, 65535)]
+    lam, mu = torch.cat([q[0] for q in parts]), torch.cat([q[1] for q in parts])
+    xd = torch.as_tensor(x, device=dev)
+
+    def free_sim(b0, n_start, seed_, cap):
+        return ops.simulate_dd_batch(par, xd[b0:], spb, n_start, seed_, mb, md, capacity=cap, device=dev)
+
+    def step_sim(b0, n1, seed_, cap):
+        nf = n_bins - b0
+        return ops.simulate_dd_batch(par.repeat(nf, 1), xd[b0:].repeat_interleave(R)[:, None], spb, n1, seed_, mb, md,
+                                     capacity=cap, device=dev)
+
+    div_obs, b0, cap, free, step, table, fit = _check(R, sp, ex, spb, seed, free_sim, step_sim, start_bin, capacity, start_time)
+    return PpcResult(idx, lam.cpu().numpy(), mu.cpu().numpy(), div_obs, b0, int(div_obs[b0]), cap, (seed, seed + R), free,
+                     step, table, fit)
 
 
 def write_tables(stem, table, fit):
@@ -225,17 +326,55 @@ def write_run_ppc(eng, sp_events, ex_events, n_local, total_chains, world, rank,
                   start_bin=None):
     """LiteRateForward.py's --ppc: the check on the rows the run sampled, int(burnin * S) dropped per chain, on rank 0
     (the rows are gathered to its device once when the chains are sharded) -> the two files and one line on stdout."""
-    from . import dist as lrd
-    S = eng.samples_done()
-    burn = int(burnin * S)
-    local = eng.trace[burn:S][:, :n_local]
-    rows = lrd.gather_traces(local.contiguous(), total_chains) if world > 1 else local
+    rows = _gathered_rows(eng, n_local, total_chains, world, burnin)
     if rank != 0:
         return None
     res = posterior_predictive(rows, sp_events, ex_events, n_draws, steps_per_bin, seed, start_bin=start_bin,
                                start_time=np.floor(eng.start_time))
+    return _write_and_say(stem, res)
+
+
+def _write_and_say(stem, res):
     write_tables(stem, res.table, res.fit)
     print("posterior predictive check: %s_PPC.tsv, %s_PPC_fit.tsv (%d draws from bin %d; overflowed: %d free-running, "
           "%d one-step)" % (stem, stem, res.fit["draws"], res.start_bin, res.fit["free_overflowed"],
                             res.fit["step_overflowed"]))
     return res
+
+
+def _gathered_rows(eng, n_local, total_chains, world, burnin):
+    """the post-burn-in rows of all chains, [S', total_chains, LR_TRACE_W], on this rank's device (every rank calls)"""
+    from . import dist as lrd
+    S = eng.samples_done()
+    local = eng.trace[int(burnin * S):S][:, :n_local]
+    return lrd.gather_traces(local.contiguous(), total_chains) if world > 1 else local
+
+
+def write_run_ppc_dd(eng, n_local, total_chains, world, rank, burnin, n_draws, steps_per_bin, seed, stem, start_bin=None):
+    """DDRate.py's --ppc: posterior_predictive_dd on the rows the run sampled, int(burnin * S) dropped per chain, against
+    create_bins' event counts, on rank 0 -> the two files and one line on stdout."""
+    rows = _gathered_rows(eng, n_local, total_chains, world, burnin)
+    if rank != 0:
+        return None
+    res = posterior_predictive_dd(rows, eng.n_spec, eng.n_exti, eng.DT, eng.time_range, eng.m_birth, eng.m_death, n_draws,
+                                  steps_per_bin, seed, start_bin=start_bin, start_time=float(eng.origin))
+    return _write_and_say(stem, res)
+
+
+def write_run_ppc_trend(eng, n_local, total_chains, world, rank, burnin, n_draws, steps_per_bin, seed, stem, start_bin=None):
+    """trend_rate.py's --ppc: the rates of the drawn rows by ops.trend_rates (fixed per bin: the covariate is data), then
+    posterior_predictive_rates, on rank 0 -> the two files and one line on stdout."""
+    from . import ops
+    import torch
+    rows = _gathered_rows(eng, n_local, total_chains, world, burnin)
+    if rank != 0:
+        return None
+    flat = rows.reshape(-1, LR_TRACE_W)
+    idx = draw_indices(flat.shape[0], n_draws)
+    par = flat[torch.as_tensor(idx, device=flat.device)][:, 4:10].contiguous()
+    # (lr_trend_rates takes at most 65535 parameter vectors a launch)
+    parts = [ops.trend_rates(par[a:a + 65535], eng.trend, eng.const_birth, eng.const_death) for a in range(0, len(idx), 65535)]
+    lam, mu = torch.cat([q[0] for q in parts]), torch.cat([q[1] for q in parts])
+    res = posterior_predictive_rates(lam, mu, eng.n_spec, eng.n_exti, steps_per_bin, seed, start_bin=start_bin,
+                                     start_time=float(eng.origin), draw_rows=idx)
+    return _write_and_say(stem, res)
