@@ -74,6 +74,12 @@ def build_parser():
     p.add_argument('--ppc_scale', type=int, default=100, help='simulation steps per time unit (the reference Simulator.scale)')
     p.add_argument('--ppc_start_bin', type=int, default=-1, help='bin at whose left edge the free-running simulations start '
                    '(default: the first bin after bin 0 that starts with an observed lineage)')
+    p.add_argument('--waic', type=float, default=-1.0, help='after the run, write <stem>_WAIC.tsv and <stem>_WAIC_pointwise.npz next to the logs: WAIC (elpd, '
+                   'p_waic and their standard errors) from --waic_draws posterior draws of the rates (this burn-in '
+                   'fraction dropped per chain), the log-likelihood term of each lineage reduced over the draws on the GPU; '
+                   'rank runs of the same program on the same data with `python -m literate_amd.waic '
+                   'A_WAIC_pointwise.npz B_WAIC_pointwise.npz`; not with -model_BDI 1 or -pyrate_output')
+    p.add_argument('--waic_draws', type=int, default=1000, help='posterior draws WAIC is computed from (at least 2)')
     p.add_argument('--init_shifts', type=int, default=0, help='initial number of rate shifts per process')
     p.add_argument('--block', type=int, default=0, help='iterations per device window: logs are written and flushed and '
                    'the state is printed once per window, while the next one runs (default: -p rounded up to ~50000)')
@@ -132,6 +138,11 @@ def main(argv=None):
             raise SystemExit(err)
         if args.ppc_draws < 1 or args.ppc_scale < 1:
             raise SystemExit("--ppc_draws and --ppc_scale must be at least 1")
+    if args.waic != -1.0:
+        from literate_amd.waic import arg_error as waic_arg_error
+        err = waic_arg_error(args.waic, args.waic_draws, model=args.model_BDI, pyrate_output=args.pyrate_output)
+        if err:
+            raise SystemExit(err)
     print("\n\n             LiteRate - 20200206 (MI355X engine)\n")
     import torch
     import torch.distributed as dist
@@ -261,6 +272,10 @@ def main(argv=None):
         stem = logs.log_paths(args.d, args.model_BDI, args.out)[1]["div"][:-len("_div.log")]
         ppc.write_run_ppc(eng, sp, ex, n_local, args.chains, world, rank, args.ppc, args.ppc_draws, args.ppc_scale, rseed,
                           stem, start_bin=args.ppc_start_bin if args.ppc_start_bin >= 0 else None)
+    if args.waic != -1.0 and n_samples:
+        from literate_amd import waic
+        stem = logs.log_paths(args.d, args.model_BDI, args.out)[1]["div"][:-len("_div.log")]
+        waic.write_run_waic(eng, n_local, args.chains, world, rank, args.waic, args.waic_draws, stem)
     eng.close()
     if world > 1:
         dist.destroy_process_group()

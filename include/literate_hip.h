@@ -352,6 +352,32 @@ int lr_curve_summary(const double* rows, int32_t n_samples, int32_t n_chains, in
                      int32_t sampler, int32_t m_birth, int32_t m_death, const double* aux, int32_t n_bins, double burnin,
                      int32_t pooled, double* out, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- Model comparison: pointwise WAIC over posterior draws (Watanabe 2010; Vehtari, Gelman & Gabry 2017) ------------
+ * l[i, s] = the term lr_bd_loglik_batch adds for lineage i under draw s (lam_bins / mu_bins [n_draws, n_bins]), models 0, 2
+ * and 3 (model 1 carries a per-bin constant that belongs to no lineage: LR_ERR_MODEL).  Per lineage, over the S draws:
+ *   lppd_i = m_i + log(1/S sum_s exp(l[i, s] - m_i)), m_i = max_s l[i, s];  mean_i = 1/S sum_s l[i, s];
+ *   var_i  = sum_s (l[i, s] - mean_i)^2 / (S - 1)      (running maximum with a rescaled sum; Welford / Chan moments)
+ * out_pointwise [n, 3] = (lppd_i, mean_i, var_i) in input order.  A lineage with any non-finite l[i, s] (a zero rate gives
+ * -inf, a nan rate nan) is FLAGGED: its three outputs are NaN and it is left out of the totals.
+ * out_totals [8]: 0 lineages used, 1 lineages flagged, 2 lppd = sum lppd_i, 3 p_waic = sum var_i, 4 elpd_waic =
+ *   sum (lppd_i - var_i), 5 se_elpd = sqrt(used * sample variance over i of (lppd_i - var_i)) (NaN when used < 2),
+ *   6 the number of used lineages with var_i > 0.4, 7 max_i var_i (NaN when none is used).
+ * The [n, S] matrix is never stored: a block owns plan[0] lineages and walks the draws, whose tables pass through
+ * LDS plan[1] at a time; on few lineages the draws are split into plan[2] slices (grid.y) whose per-lineage states a
+ * second kernel merges in slice order.  lr_waic_plan: out (host int32[4]) = {lineages per tile, draws per LDS chunk, draw
+ * slices, tiles}, a function of (n, n_bins, n_draws, model) alone; every sum has a fixed order, so the same inputs give
+ * the same bits.  LR_WAIC_SLICES=k in the environment (read at every call; for tests and measurements) asks for k slices
+ * instead of the plan's own count (at most n_draws; slices of ceil(n_draws / k) draws).
+ * Errors before any launch: n < 1 or n_draws < 2 or an n_bins lr_bd_loglik_batch refuses -> LR_ERR_SIZE; model 1 or
+ * unknown, or model 0 without br_length -> LR_ERR_MODEL; t0 not integer valued -> LR_ERR_T0; LR_ERR_WORKSPACE.          */
+int64_t lr_waic_workspace_bytes(int64_t n, int32_t n_bins, int32_t n_draws, int32_t model);
+int lr_waic_plan(int64_t n, int32_t n_bins, int32_t n_draws, int32_t model, int32_t* out /* host int32[4] */);
+int lr_waic_pointwise(const double* ts, const double* te, int64_t n, double t0, int32_t n_bins,
+                      const double* lam_bins /* [n_draws, n_bins] */, const double* mu_bins, int32_t n_draws,
+                      int32_t model, const double* br_length, double end_time,
+                      double* out_pointwise /* [n, 3] */, double* out_totals /* [8] */,
+                      void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- A11: fused multi-chain RJMCMC --------------------------------------------------------
  * Replaces runMCMC (LRF:216-373) for n_chains independent chains.  Per iteration: one scan of
  * the lineage arrays scoring every chain's proposal, then one chain-step kernel (reduce,

@@ -58,6 +58,10 @@ SIGNATURES = {
     "lr_bd_loglik_plan": (c_i32, [c_i64, c_i32, c_i32, c_i32, C.POINTER(c_i32)]),
     "lr_bd_loglik_batch": (c_i32, [c_vp, c_vp, c_i64, c_f64, c_i32, c_vp, c_vp, c_i32, c_i32, c_vp, c_f64, c_vp,
                                    c_vp, c_i64, c_vp]),
+    "lr_waic_workspace_bytes": (c_i64, [c_i64, c_i32, c_i32, c_i32]),
+    "lr_waic_plan": (c_i32, [c_i64, c_i32, c_i32, c_i32, C.POINTER(c_i32)]),
+    "lr_waic_pointwise": (c_i32, [c_vp, c_vp, c_i64, c_f64, c_i32, c_vp, c_vp, c_i32, c_i32, c_vp, c_f64, c_vp, c_vp, c_vp,
+                                  c_i64, c_vp]),
     "lr_rj_propose_score": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_f64, c_vp, c_vp, c_vp, c_vp,
                                     c_vp]),
     "lr_log_priors": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_f64, c_vp, c_vp, c_vp, c_vp]),

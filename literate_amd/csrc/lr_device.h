@@ -323,4 +323,33 @@ __device__ inline double lr_build_tables_wave(const double* __restrict__ lam_bin
     return lr_wave_sum(csum);
 }
 
-
+// ---------------------------------------------------------------------------------------
+// one lineage against the CB general tables (LR_TAB_GENERAL) at lds, lds + tab_stride, ...: acc[c] += its term under
+// table c.  Shared by the launch-based scan (lr_loglik.hip) and the pointwise WAIC pass (lr_waic.hip), which keeps the
+// terms apart per lineage instead of summing them per chain.
+// ---------------------------------------------------------------------------------------
+template <int CB>
+__device__ __forceinline__ void lr_score_lineage(double s, double e, double t0, double nb1, int H, int n_cls,
+                                                 double end_time, const double2* __restrict__ lds, int tab_stride,
+                                                 double (&acc)[CB]) {
+    const double fl = floor(s);
+    const double ce = ceil(e);
+    // table index: births [lo,hi) -> floor, deaths (lo,hi] -> ceil-1; 0 / n_bins+1 = outside
+    const int js = (int)fmin(fmax(fl - t0 + 1.0, 0.0), nb1);
+    const int je = (int)fmin(fmax(ce - t0, 0.0), nb1);
+    const double fs = s - fl;
+    const double fe = e - (ce - 1.0);
+    int base = 0;
+    if (n_cls == 2 && e >= end_time) base = 2 * H;
+    const int offS = base + js;
+    const int offE = base + H + je;
+#pragma unroll
+    for (int c = 0; c < CB; ++c) {
+        const double2 S = lds[c * tab_stride + offS];
+        const double2 E = lds[c * tab_stride + offE];
+        double t = S.x + E.x;
+        t = fma(fs, S.y, t);
+        t = fma(fe, E.y, t);
+        acc[c] += t;
+    }
+}

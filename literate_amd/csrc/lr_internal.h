@@ -40,6 +40,11 @@ static inline __host__ __device__ int lr_tile_stride(int tiles) { return (tiles 
 int lr_launch_scan(const lr_scan_plan& plan, const double* ts, const double* te, long long n, double t0, int n_bins,
                    double end_time, const double2* tables, int n_chains, double* partials, int partial_stride,
                    hipStream_t stream);
+// enqueue lr_build_tables_kernel (lr_loglik.hip) for `n_chains` rate vectors: tables[c * tab_stride ...] in the general
+// layout (lr_device.h), consts[c] = the chain constant
+int lr_launch_build_tables(const double* lam_bins, const double* mu_bins, const double* br_length, int model, int n_bins,
+                           int n_cls, int H, int tab_stride, int n_chains, double2* tables, double* consts,
+                           hipStream_t stream);
 // can the engine use the fused scan|step kernel for this plan?  (instantiated for a subset of shapes)
 static inline bool lr_fused_supported(const lr_scan_plan& p) {
     if (!p.fast) return false;

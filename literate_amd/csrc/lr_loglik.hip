@@ -29,35 +29,18 @@ __global__ __launch_bounds__(LR_WAVE) void lr_build_tables_kernel(const double* 
     if (lane == 0) consts[c] = cst;
 }
 
+// the same launch for the other translation units of the library (lr_waic.hip): tables [n_chains, tab_stride], consts [n_chains]
+int lr_launch_build_tables(const double* lam_bins, const double* mu_bins, const double* br_length, int model, int n_bins,
+                           int n_cls, int H, int tab_stride, int n_chains, double2* tables, double* consts,
+                           hipStream_t stream) {
+    hipLaunchKernelGGL(lr_build_tables_kernel, dim3(n_chains), dim3(LR_WAVE), 0, stream, lam_bins, mu_bins, br_length, model,
+                       n_bins, n_cls, H, tab_stride, tables, consts);
+    return (int)hipGetLastError();
+}
+
 // ------------------------------------------------------------------------------------------
 // the lineage scan
 // ------------------------------------------------------------------------------------------
-template <int CB>
-__device__ __forceinline__ void lr_score_lineage(double s, double e, double t0, double nb1, int H, int n_cls,
-                                                 double end_time, const double2* __restrict__ lds, int tab_stride,
-                                                 double (&acc)[CB]) {
-    const double fl = floor(s);
-    const double ce = ceil(e);
-    // table index: births [lo,hi) -> floor, deaths (lo,hi] -> ceil-1; 0 / n_bins+1 = outside
-    const int js = (int)fmin(fmax(fl - t0 + 1.0, 0.0), nb1);
-    const int je = (int)fmin(fmax(ce - t0, 0.0), nb1);
-    const double fs = s - fl;
-    const double fe = e - (ce - 1.0);
-    int base = 0;
-    if (n_cls == 2 && e >= end_time) base = 2 * H;
-    const int offS = base + js;
-    const int offE = base + H + je;
-#pragma unroll
-    for (int c = 0; c < CB; ++c) {
-        const double2 S = lds[c * tab_stride + offS];
-        const double2 E = lds[c * tab_stride + offE];
-        double t = S.x + E.x;
-        t = fma(fs, S.y, t);
-        t = fma(fe, E.y, t);
-        acc[c] += t;
-    }
-}
-
 template <int CB>
 __global__ __launch_bounds__(LR_SCAN_THREADS) void lr_scan_kernel(const double* __restrict__ ts,
                                                                   const double* __restrict__ te, long long n,

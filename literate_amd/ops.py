@@ -171,6 +171,50 @@ def bd_loglik_batch(ts, te, t0, lam_bins, mu_bins, model=2, br_length=None, end_
     return out
 
 
+WAIC_TOTALS = ("lineages_used", "lineages_flagged", "lppd", "p_waic", "elpd_waic", "se_elpd", "n_var_gt_0.4", "max_var")
+WAIC_PLAN = ("lineages_per_tile", "draws_per_chunk", "draw_slices", "tiles")
+
+
+def waic_plan(n, n_bins, n_draws, model=2):
+    """lr_waic_plan: (lineages per tile, draws per LDS chunk, draw slices, tiles) - a function of the sizes alone (host)."""
+    import ctypes as C
+    import torch  # noqa: F401  (before the library, as everywhere here: both must bind the HIP runtime torch ships)
+    lib = _hip.load()
+    out = (C.c_int32 * 4)()
+    _hip.check(lib.lr_waic_plan(int(n), int(n_bins), int(n_draws), int(model), out), "lr_waic_plan")
+    return tuple(int(v) for v in out)
+
+
+def waic_pointwise(ts, te, t0, lam_bins, mu_bins, model=2, br_length=None, end_time=0.0):
+    """Pointwise WAIC terms of S posterior draws of per-bin rates [S, n_bins] (lr_waic_pointwise): returns
+    (pointwise [n, 3] = lppd_i, mean_i, var_i - NaN where a lineage's term is not finite under some draw -,
+    totals [8] (WAIC_TOTALS), plan (WAIC_PLAN, host tuple)), tensors on the device.  The [n, S] matrix of terms is never
+    stored.  Models 0, 2 and 3."""
+    torch = _torch()
+    lib = _hip.load()
+    ts = _dev(ts, torch.float64)
+    te = _dev(te, torch.float64, ts.device)
+    lam, mu = _dev(lam_bins, torch.float64, ts.device), _dev(mu_bins, torch.float64, ts.device)
+    if lam.dim() != 2 or mu.shape != lam.shape or te.numel() != ts.numel() or ts.dim() != 1:
+        raise ValueError("shape mismatch: ts, te [n]; lam_bins, mu_bins [draws, n_bins]")
+    S, n_bins = lam.shape
+    n = ts.numel()
+    br = None if br_length is None else _dev(br_length, torch.float64, ts.device)
+    if br is not None and br.numel() != n_bins:
+        raise ValueError("br_length must have n_bins entries")
+    nbytes = lib.lr_waic_workspace_bytes(n, n_bins, S, int(model))
+    if nbytes < 0:
+        _hip.check(int(nbytes), "lr_waic_workspace_bytes")
+    plan = waic_plan(n, n_bins, S, model)
+    pw = torch.empty((n, 3), dtype=torch.float64, device=ts.device)
+    tot = torch.empty(8, dtype=torch.float64, device=ts.device)
+    ws = _workspace(nbytes, ts.device)
+    rc = _hip.launch(lib.lr_waic_pointwise, ts.device, _hip.ptr(ts), _hip.ptr(te), n, float(t0), n_bins, _hip.ptr(lam), _hip.ptr(mu),
+                     S, int(model), _hip.ptr(br), float(end_time), _hip.ptr(pw), _hip.ptr(tot), _hip.ptr(ws), ws.numel())
+    _hip.check(rc, "lr_waic_pointwise")
+    return pw, tot, plan
+
+
 class LoglikSession:
     """The calc_likelihood seam (LRF:305-308: one call per MCMC iteration) with everything that does not change
     between calls prepared once: lineages and workspace resident in HBM, ONE pinned staging buffer for what a call may

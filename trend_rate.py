@@ -46,6 +46,13 @@ def build_parser():
     p.add_argument('--ppc_scale', type=int, default=100, help='simulation steps per time unit (the reference Simulator.scale)')
     p.add_argument('--ppc_start_bin', type=int, default=-1, help='bin at whose left edge the free-running simulations start '
                    '(default: the first bin after bin 0 that starts with an observed lineage)')
+    p.add_argument('--waic', type=float, default=-1.0, help='after the run, write <stem>_WAIC.tsv and <stem>_WAIC_pointwise.npz beside the logs: WAIC (elpd, '
+                   'p_waic and their standard errors) from --waic_draws posterior draws of the parameters, at the '
+                   'per-bin rates the trend gives them (this burn-in fraction dropped per chain), the per-lineage '
+                   'log-likelihood term reduced over the draws on the GPU; rank runs of the same program on the same '
+                   'data with `python -m literate_amd.waic A_WAIC_pointwise.npz B_WAIC_pointwise.npz`; not with '
+                   '-rm_first_bin 1 (extension)')
+    p.add_argument('--waic_draws', type=int, default=1000, help='posterior draws WAIC is computed from (at least 2)')
     p.add_argument('--block', type=int, default=0, help='iterations per device window (logs are flushed once per window; '
                    'default: -p rounded up to ~50000)')
     return p
@@ -66,6 +73,11 @@ def main(argv=None):
     if args.ppc != -1.0:
         from literate_amd.ppc import dd_arg_error
         err = dd_arg_error(args.ppc, args.rm_first_bin, args.ppc_draws, args.ppc_scale)
+        if err:
+            raise SystemExit(err)
+    if args.waic != -1.0:
+        from literate_amd.waic import arg_error as waic_arg_error
+        err = waic_arg_error(args.waic, args.waic_draws, rm_first_bin=args.rm_first_bin)
         if err:
             raise SystemExit(err)
     print("\n\n             TrendRate - 20190205 (MI355X engine)\n")
@@ -143,6 +155,10 @@ def main(argv=None):
         write_run_ppc_trend(eng, n_local, args.chains, world, rank, args.ppc, args.ppc_draws, args.ppc_scale, seed,
                             "%s_%s" % (stem, args.trend_index),
                             start_bin=args.ppc_start_bin if args.ppc_start_bin >= 0 else None)
+    if args.waic != -1.0 and n_samples:
+        from literate_amd.waic import write_run_waic_trend
+        write_run_waic_trend(eng, n_local, args.chains, world, rank, args.waic, args.waic_draws,
+                             "%s_%s" % (stem, args.trend_index))
     eng.close()
     if world > 1:
         dist.barrier()
