@@ -50,6 +50,12 @@ def build_parser():
                    'the same data with `python -m literate_amd.waic A_WAIC_pointwise.npz B_WAIC_pointwise.npz`; not with '
                    '-rm_first_bin 1 (extension)')
     p.add_argument('--waic_draws', type=int, default=1000, help='posterior draws WAIC is computed from (at least 2)')
+    p.add_argument('--loo', type=float, default=-1.0, help='after the run, write <stem>_LOO.tsv and <stem>_LOO_pointwise.npz beside the logs: PSIS-LOO '
+                   '(Pareto-smoothed leave-one-out: elpd_loo, p_loo, their standard errors and the Pareto k of every lineage) '
+                   'from --loo_draws posterior draws, chosen and scored as --waic does (this burn-in fraction dropped per '
+                   'chain), every lineage\'s draws sorted, fitted and smoothed on the GPU; rank runs of the same program on '
+                   'the same data with `python -m literate_amd.loo A_LOO_pointwise.npz B_LOO_pointwise.npz`; not with -rm_first_bin 1 (extension)')
+    p.add_argument('--loo_draws', type=int, default=1000, help='posterior draws PSIS-LOO is computed from (2 to 8192)')
     p.add_argument('--block', type=int, default=0, help='iterations per device window (logs are flushed once per window; '
                    'default: -p rounded up to ~50000)')
     return p
@@ -75,6 +81,11 @@ def main(argv=None):
     if args.waic != -1.0:
         from literate_amd.waic import arg_error as waic_arg_error
         err = waic_arg_error(args.waic, args.waic_draws, rm_first_bin=args.rm_first_bin)
+        if err:
+            raise SystemExit(err)
+    if args.loo != -1.0:
+        from literate_amd.loo import arg_error as loo_arg_error
+        err = loo_arg_error(args.loo, args.loo_draws, rm_first_bin=args.rm_first_bin)
         if err:
             raise SystemExit(err)
     import torch
@@ -152,6 +163,9 @@ def main(argv=None):
     if args.waic != -1.0 and n_samples:
         from literate_amd.waic import write_run_waic_dd
         write_run_waic_dd(eng, n_local, args.chains, world, rank, args.waic, args.waic_draws, stem)
+    if args.loo != -1.0 and n_samples:
+        from literate_amd.loo import write_run_loo_dd
+        write_run_loo_dd(eng, n_local, args.chains, world, rank, args.loo, args.loo_draws, stem)
     eng.close()
     if world > 1:
         dist.barrier()

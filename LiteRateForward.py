@@ -80,6 +80,12 @@ def build_parser():
                    'rank runs of the same program on the same data with `python -m literate_amd.waic '
                    'A_WAIC_pointwise.npz B_WAIC_pointwise.npz`; not with -model_BDI 1 or -pyrate_output')
     p.add_argument('--waic_draws', type=int, default=1000, help='posterior draws WAIC is computed from (at least 2)')
+    p.add_argument('--loo', type=float, default=-1.0, help='after the run, write <stem>_LOO.tsv and <stem>_LOO_pointwise.npz next to the logs: PSIS-LOO '
+                   '(Pareto-smoothed leave-one-out: elpd_loo, p_loo, their standard errors and the Pareto k of every lineage) '
+                   'from --loo_draws posterior draws, chosen and scored as --waic does (this burn-in fraction dropped per '
+                   'chain), every lineage\'s draws sorted, fitted and smoothed on the GPU; rank runs of the same program on '
+                   'the same data with `python -m literate_amd.loo A_LOO_pointwise.npz B_LOO_pointwise.npz`; not with -model_BDI 1 or -pyrate_output')
+    p.add_argument('--loo_draws', type=int, default=1000, help='posterior draws PSIS-LOO is computed from (2 to 8192)')
     p.add_argument('--init_shifts', type=int, default=0, help='initial number of rate shifts per process')
     p.add_argument('--block', type=int, default=0, help='iterations per device window: logs are written and flushed and '
                    'the state is printed once per window, while the next one runs (default: -p rounded up to ~50000)')
@@ -141,6 +147,11 @@ def main(argv=None):
     if args.waic != -1.0:
         from literate_amd.waic import arg_error as waic_arg_error
         err = waic_arg_error(args.waic, args.waic_draws, model=args.model_BDI, pyrate_output=args.pyrate_output)
+        if err:
+            raise SystemExit(err)
+    if args.loo != -1.0:
+        from literate_amd.loo import arg_error as loo_arg_error
+        err = loo_arg_error(args.loo, args.loo_draws, model=args.model_BDI, pyrate_output=args.pyrate_output)
         if err:
             raise SystemExit(err)
     print("\n\n             LiteRate - 20200206 (MI355X engine)\n")
@@ -276,6 +287,10 @@ def main(argv=None):
         from literate_amd import waic
         stem = logs.log_paths(args.d, args.model_BDI, args.out)[1]["div"][:-len("_div.log")]
         waic.write_run_waic(eng, n_local, args.chains, world, rank, args.waic, args.waic_draws, stem)
+    if args.loo != -1.0 and n_samples:
+        from literate_amd import loo
+        stem = logs.log_paths(args.d, args.model_BDI, args.out)[1]["div"][:-len("_div.log")]
+        loo.write_run_loo(eng, n_local, args.chains, world, rank, args.loo, args.loo_draws, stem)
     eng.close()
     if world > 1:
         dist.destroy_process_group()

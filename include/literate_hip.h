@@ -378,6 +378,47 @@ int lr_waic_pointwise(const double* ts, const double* te, int64_t n, double t0, 
                       double* out_pointwise /* [n, 3] */, double* out_totals /* [8] */,
                       void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- Model comparison: PSIS-LOO over posterior draws (Vehtari, Gelman & Gabry 2017; Vehtari, Simpson, Gelman, Yao &
+ * Gabry, "Pareto smoothed importance sampling"; the fit: Zhang & Stephens 2009 as loo::gpdfit) --------------------------
+ * Per row (a lineage) of S = n_draws log-likelihood terms l[s], with r = -l the log importance ratios, rmax = max r:
+ *   M = min(floor(0.2 S), ceil(3 sqrt S)) (relative efficiency 1).  The draws sorted ascending by (r, draw index): the
+ *   last M are the tail t_1 <= ... <= t_M, the one below them the cutoff c (M = 0: c = rmax).
+ *   M < 5 or t_M == t_1: nothing is smoothed, pareto_k = +inf.  Otherwise x_j = exp(t_j - rmax) - exp(c - rmax) and the
+ *   generalized Pareto fit on m = 30 + floor(sqrt M) grid points theta_j = 1/x_M + (1 - sqrt(m / (j - 1/2))) / (3 x_q),
+ *   q = floor(M/4 + 1/2): k(theta) = mean log1p(-theta x), ell_j = M (log(-theta_j / k_j) - k_j - 1),
+ *   w_j = 1 / sum_i exp(ell_i - ell_j), theta^ = sum theta_j w_j, k = k(theta^), sigma = -k / theta^.  The tail's log weights
+ *   become min(log(sigma expm1(-k log1p(-p_j)) / k + exp(c - rmax)), 0), p_j = (j - 1/2) / M (k == 0: -sigma log1p(-p_j)),
+ *   in the tail's sorted order; every other draw keeps r - rmax.  A k or sigma that is not finite leaves the raw weights
+ *   and reports +inf.  Reported pareto_k = (M k + 5) / (M + 10).
+ *   elpd_loo = logsumexp(l + lw) - logsumexp(lw), evaluated as (max(l + lw) - max lw) + log(sum / sum);
+ *   lppd = max l + log(1/S sum exp(l - max l));  n_eff = 1 / sum of the squared normalised weights.
+ * out_pointwise [n, 4] = (elpd_loo, pareto_k, lppd, n_eff) in input order; a row with any non-finite term is FLAGGED:
+ * four NaN, left out of the totals.
+ * out_totals [10]: 0 rows used, 1 flagged, 2 elpd_loo, 3 se_elpd = sqrt(used * sample variance of elpd_loo_i) (NaN when
+ *   used < 2), 4 p_loo = sum (lppd_i - elpd_loo_i), 5 lppd, 6 rows with finite k > 0.5, 7 with finite k > 0.7, 8 unsmoothed
+ *   rows (k = +inf), 9 the largest finite k (NaN when there is none); 2, 4 and 5 are NaN when no row is used.
+ * lr_psis_rows takes any row-major matrix of pointwise log-likelihoods that lives on the device.  Its workspace receives
+ * the tail's draw indices, int32 [n_rows, max(M, 1)] in the tail's sorted order (-1 in a flagged row).
+ * lr_loo_pointwise computes the terms of lr_waic_pointwise for a batch of plan[2] lineages into a [batch, n_draws] slab at
+ * the START of the workspace (at most 64 MiB; whole tiles of 512 when n does not fit one slab), smooths its rows, and goes
+ * on to the next batch; lr_loo_plan: out (host int32[4]) = {M, m (0 without a fit), lineages per batch, batches}.
+ * LR_LOO_BATCH=b in the environment (read at every call; for tests and measurements) forces min(b, n) lineages per batch.
+ * One workgroup sorts one row in LDS (a bitonic network over n_draws padded to a power of two): 2 <= n_draws <= 8192.
+ * Every sum has a fixed order; a row's outputs depend on the row alone, not on the batch or the other rows.
+ * Errors before any launch, in the order of lr_waic_pointwise: LR_ERR_NULL; n < 1, n_draws outside [2, 8192] or an n_bins
+ * lr_bd_loglik_batch refuses -> LR_ERR_SIZE; LR_ERR_MODEL; LR_ERR_T0; LR_ERR_WORKSPACE.                                */
+int64_t lr_loo_workspace_bytes(int64_t n, int32_t n_bins, int32_t n_draws, int32_t model);
+int lr_loo_plan(int64_t n, int32_t n_bins, int32_t n_draws, int32_t model, int32_t* out /* host int32[4] */);
+int lr_loo_pointwise(const double* ts, const double* te, int64_t n, double t0, int32_t n_bins,
+                     const double* lam_bins /* [n_draws, n_bins] */, const double* mu_bins, int32_t n_draws,
+                     int32_t model, const double* br_length, double end_time,
+                     double* out_pointwise /* [n, 4] */, double* out_totals /* [10] */,
+                     void* workspace, int64_t workspace_bytes, void* stream);
+int64_t lr_psis_rows_workspace_bytes(int64_t n_rows, int32_t n_draws);
+int lr_psis_rows(const double* loglik /* device [n_rows, n_draws], row-major */, int64_t n_rows, int32_t n_draws,
+                 double* out_pointwise /* [n_rows, 4] */, double* out_totals /* [10] */,
+                 void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- A11: fused multi-chain RJMCMC --------------------------------------------------------
  * Replaces runMCMC (LRF:216-373) for n_chains independent chains.  Per iteration: one scan of
  * the lineage arrays scoring every chain's proposal, then one chain-step kernel (reduce,

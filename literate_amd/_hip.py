@@ -62,6 +62,12 @@ SIGNATURES = {
     "lr_waic_plan": (c_i32, [c_i64, c_i32, c_i32, c_i32, C.POINTER(c_i32)]),
     "lr_waic_pointwise": (c_i32, [c_vp, c_vp, c_i64, c_f64, c_i32, c_vp, c_vp, c_i32, c_i32, c_vp, c_f64, c_vp, c_vp, c_vp,
                                   c_i64, c_vp]),
+    "lr_loo_workspace_bytes": (c_i64, [c_i64, c_i32, c_i32, c_i32]),
+    "lr_loo_plan": (c_i32, [c_i64, c_i32, c_i32, c_i32, C.POINTER(c_i32)]),
+    "lr_loo_pointwise": (c_i32, [c_vp, c_vp, c_i64, c_f64, c_i32, c_vp, c_vp, c_i32, c_i32, c_vp, c_f64, c_vp, c_vp, c_vp,
+                                 c_i64, c_vp]),
+    "lr_psis_rows_workspace_bytes": (c_i64, [c_i64, c_i32]),
+    "lr_psis_rows": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp]),
     "lr_rj_propose_score": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_f64, c_vp, c_vp, c_vp, c_vp,
                                     c_vp]),
     "lr_log_priors": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_f64, c_vp, c_vp, c_vp, c_vp]),

@@ -215,6 +215,83 @@ def waic_pointwise(ts, te, t0, lam_bins, mu_bins, model=2, br_length=None, end_t
     return pw, tot, plan
 
 
+LOO_TOTALS = ("lineages_used", "lineages_flagged", "elpd_loo", "se_elpd", "p_loo", "lppd", "n_k_gt_0.5", "n_k_gt_0.7",
+              "n_unsmoothed", "max_k")
+LOO_POINTWISE = ("elpd_loo", "pareto_k", "lppd", "n_eff")
+LOO_PLAN = ("tail_length", "grid_points", "lineages_per_batch", "batches")
+
+
+def loo_plan(n, n_bins, n_draws, model=2):
+    """lr_loo_plan: (tail length M, grid points m of the fit - 0 without one -, lineages per batch, batches): a function of
+    the sizes alone (host; LR_LOO_BATCH in the environment is read per call)."""
+    import ctypes as C
+    import torch  # noqa: F401  (before the library, as everywhere here: both must bind the HIP runtime torch ships)
+    lib = _hip.load()
+    out = (C.c_int32 * 4)()
+    _hip.check(lib.lr_loo_plan(int(n), int(n_bins), int(n_draws), int(model), out), "lr_loo_plan")
+    return tuple(int(v) for v in out)
+
+
+def loo_pointwise(ts, te, t0, lam_bins, mu_bins, model=2, br_length=None, end_time=0.0, return_terms=False):
+    """PSIS-LOO of S posterior draws of per-bin rates [S, n_bins] (lr_loo_pointwise): returns (pointwise [n, 4] =
+    elpd_loo_i, pareto_k_i, lppd_i, n_eff_i - NaN where a lineage's term is not finite under some draw -, totals [10]
+    (LOO_TOTALS), plan (LOO_PLAN, host tuple)), tensors on the device.  Models 0, 2 and 3; 2 <= S <= 8192.
+    return_terms (a test hook; one batch only): also a copy of the [n, S] matrix of terms the first stage wrote."""
+    torch = _torch()
+    lib = _hip.load()
+    ts = _dev(ts, torch.float64)
+    te = _dev(te, torch.float64, ts.device)
+    lam, mu = _dev(lam_bins, torch.float64, ts.device), _dev(mu_bins, torch.float64, ts.device)
+    if lam.dim() != 2 or mu.shape != lam.shape or te.numel() != ts.numel() or ts.dim() != 1:
+        raise ValueError("shape mismatch: ts, te [n]; lam_bins, mu_bins [draws, n_bins]")
+    S, n_bins = lam.shape
+    n = ts.numel()
+    br = None if br_length is None else _dev(br_length, torch.float64, ts.device)
+    if br is not None and br.numel() != n_bins:
+        raise ValueError("br_length must have n_bins entries")
+    nbytes = lib.lr_loo_workspace_bytes(n, n_bins, S, int(model))
+    if nbytes < 0:
+        _hip.check(int(nbytes), "lr_loo_workspace_bytes")
+    plan = loo_plan(n, n_bins, S, model)
+    pw = torch.empty((n, 4), dtype=torch.float64, device=ts.device)
+    tot = torch.empty(10, dtype=torch.float64, device=ts.device)
+    ws = _workspace(nbytes, ts.device)
+    rc = _hip.launch(lib.lr_loo_pointwise, ts.device, _hip.ptr(ts), _hip.ptr(te), n, float(t0), n_bins, _hip.ptr(lam), _hip.ptr(mu),
+                     S, int(model), _hip.ptr(br), float(end_time), _hip.ptr(pw), _hip.ptr(tot), _hip.ptr(ws), ws.numel())
+    _hip.check(rc, "lr_loo_pointwise")
+    if return_terms:
+        if plan[3] != 1:
+            raise ValueError("return_terms: the call took %d batches; the workspace holds the last one only" % plan[3])
+        return pw, tot, plan, ws[:n * S * 8].view(torch.float64).reshape(n, S).clone()
+    return pw, tot, plan
+
+
+def psis_loo_rows(loglik, return_tail=False):
+    """PSIS-LOO of a pointwise log-likelihood matrix [n_rows, S] (lr_psis_rows): (pointwise [n_rows, 4] (LOO_POINTWISE),
+    totals [10] (LOO_TOTALS)) on the device.  return_tail: also the tail's draw indices int32 [n_rows, M] in the tail's
+    sorted order (-1 in a flagged row), which the call leaves in its workspace."""
+    torch = _torch()
+    lib = _hip.load()
+    L = _dev(loglik, torch.float64)
+    if L.dim() != 2:
+        raise ValueError("loglik must be [n_rows, draws]")
+    n, S = L.shape
+    nbytes = lib.lr_psis_rows_workspace_bytes(n, S)
+    if nbytes < 0:
+        _hip.check(int(nbytes), "lr_psis_rows_workspace_bytes")
+    pw = torch.empty((n, 4), dtype=torch.float64, device=L.device)
+    tot = torch.empty(10, dtype=torch.float64, device=L.device)
+    ws = _workspace(nbytes, L.device)
+    rc = _hip.launch(lib.lr_psis_rows, L.device, _hip.ptr(L), n, S, _hip.ptr(pw), _hip.ptr(tot), _hip.ptr(ws), ws.numel())
+    _hip.check(rc, "lr_psis_rows")
+    if return_tail:
+        import math
+        M = min(S // 5, math.isqrt(9 * S - 1) + 1)                  # min(floor(0.2 S), ceil(3 sqrt S))
+        tail = ws[:n * max(M, 1) * 4].view(torch.int32).reshape(n, max(M, 1))[:, :M].clone()
+        return pw, tot, tail
+    return pw, tot
+
+
 class LoglikSession:
     """The calc_likelihood seam (LRF:305-308: one call per MCMC iteration) with everything that does not change
     between calls prepared once: lineages and workspace resident in HBM, ONE pinned staging buffer for what a call may
