@@ -14,7 +14,15 @@
  *     asynchronous on it and returns after enqueueing;
  *   - return value: 0 = ok, <0 = invalid argument (LR_ERR_*), >0 = a hipError_t;
  *   - arithmetic is IEEE fp64, counts are int64 (as numpy in the reference);
- *   - results are bitwise reproducible: all reductions run in a fixed order, no float atomics.
+ *   - results are bitwise reproducible: all reductions run in a fixed order, no float atomics;
+ *   - buffers may hold anything on entry: a workspace is uninitialised memory as far as the library is concerned (what a
+ *     call needs cleared it clears itself, on `stream`), and no output is read before it is written - the two exceptions
+ *     say so where they are declared (lr_shift_prior with accumulate = 1 adds to its outputs, lr_mcmc_restore resumes the
+ *     run its workspace holds).  A call touches only the first *_workspace_bytes bytes of its workspace (lr_simulate_bd:
+ *     64; the engine: lr_mcmc_layout.total_bytes) and the documented extents of its outputs, and after an argument
+ *     error (LR_ERR_NULL, _SIZE, _MODEL, _WORKSPACE, _T0) it has touched nothing: every argument check comes before the
+ *     first launch, copy or memset (tests/test_hip_abi_contract.py holds every entry point to this, on exact-size
+ *     buffers between guards).
  */
 #ifndef LITERATE_HIP_H
 #define LITERATE_HIP_H

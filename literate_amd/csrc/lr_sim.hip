@@ -17,6 +17,7 @@
 #include "lr_device.h"
 
 #define LR_P_SIM 24
+#define LR_SIM_WORKSPACE_BYTES 64      // what include/literate_hip.h documents for lr_simulate_bd
 
 struct lr_sim_step {
     long long n_cur;      // lineages existing at the start of the step
@@ -131,7 +132,9 @@ extern "C" int lr_simulate_bd(const double* lam_steps, const double* mu_steps, i
     if (mode == 0 && (!lam_steps || !mu_steps)) return LR_ERR_NULL;
     if (n_steps < 1 || n_start < 1 || capacity < n_start) return LR_ERR_SIZE;
     if (mode != 0 && (!(K > 0.0) || !(scale > 0.0))) return LR_ERR_SIZE;
-    if (workspace_bytes < (int64_t)sizeof(lr_sim_step)) return LR_ERR_WORKSPACE;
+    // the header documents 64 bytes: anything smaller is refused, not only what lr_sim_step happens to need today
+    static_assert(sizeof(lr_sim_step) <= LR_SIM_WORKSPACE_BYTES, "the documented workspace is too small");
+    if (workspace_bytes < LR_SIM_WORKSPACE_BYTES) return LR_ERR_WORKSPACE;
     hipStream_t stream = (hipStream_t)stream_;
     lr_sim_step* step = (lr_sim_step*)workspace;
     hipLaunchKernelGGL(lr_sim_init_kernel, dim3((unsigned)((n_start + 255) / 256)), dim3(256), 0, stream, ts, te,

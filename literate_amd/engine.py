@@ -81,7 +81,7 @@ class ChainEngine:
         self.layout = _hip.McmcLayout()
         with torch.cuda.device(self.device):      # the planner asks the CURRENT device for its compute units
             _hip.check(self.lib.lr_mcmc_query_layout(C.byref(self.cfg), C.byref(self.layout)), "lr_mcmc_query_layout")
-        self.workspace = torch.zeros(self.layout.total_bytes, dtype=torch.uint8, device=self.device)
+        self.workspace = ops.alloc_workspace(self.layout.total_bytes, self.device, zero=True)
         handle = C.c_void_p()
         br_ptr = _hip.ptr(self.br_length) if (model in (0, 1) or dd is not None) else None
         with torch.cuda.device(self.device):      # the library creates its streams / events on the current device

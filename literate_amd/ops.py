@@ -45,6 +45,23 @@ def _workspace(nbytes, device):
     return ws
 
 
+def alloc_workspace(nbytes, device, zero=False, cached=False):
+    """The one place a workspace of the C ABI is allocated (the wrappers here, LoglikSession, engine.ChainEngine): a uint8
+    tensor whose numel() the caller passes on as workspace_bytes.  cached: the reusable per-device buffer (_workspace, at
+    least `nbytes`); zero: cleared memory (the engine's workspace, lr_simulate_bd's 64 bytes); otherwise exactly `nbytes`
+    of uninitialised memory.  tests/helpers/abi_cases.py replaces this and alloc_output with guarded buffers."""
+    torch = _torch()
+    if cached:
+        return _workspace(nbytes, device)
+    return (torch.zeros if zero else torch.empty)(int(nbytes), dtype=torch.uint8, device=device)
+
+
+def alloc_output(shape, dtype, device, zero=False):
+    """The one place an output of the C ABI is allocated: a contiguous tensor, cleared when `zero`."""
+    torch = _torch()
+    return (torch.zeros if zero else torch.empty)(shape, dtype=dtype, device=device)
+
+
 def _unit_windows(win_lo, win_hi):
     """(t0, n_bins) when the windows are the unit bins [t0 + w, t0 + w + 1] with t0 integer valued - what the reference
     always bins into (LRF:519-523, lib create_bins) - else None.  Decided on host arrays only (no device read-back)."""
@@ -72,13 +89,13 @@ def bin_unit_events(ts, te, t0, n_bins):
     n = ts.numel()
     if te.numel() != n:
         raise ValueError("ts and te differ in length")
-    sp = torch.empty(n_bins, dtype=torch.int64, device=ts.device)
-    ex = torch.empty(n_bins, dtype=torch.int64, device=ts.device)
-    br = torch.empty(n_bins, dtype=torch.float64, device=ts.device)
+    sp = alloc_output(n_bins, torch.int64, ts.device)
+    ex = alloc_output(n_bins, torch.int64, ts.device)
+    br = alloc_output(n_bins, torch.float64, ts.device)
     nbytes = lib.lr_bin_unit_events_workspace_bytes(n, n_bins)
     if nbytes < 0:
         _hip.check(int(nbytes), "lr_bin_unit_events_workspace_bytes")
-    ws = _workspace(nbytes, ts.device)
+    ws = alloc_workspace(nbytes, ts.device, cached=True)
     rc = _hip.launch(lib.lr_bin_unit_events, ts.device, _hip.ptr(ts), _hip.ptr(te), n, float(t0), int(n_bins), _hip.ptr(sp),
                      _hip.ptr(ex), _hip.ptr(br), _hip.ptr(ws), ws.numel())
     _hip.check(rc, "lr_bin_unit_events")
@@ -100,13 +117,13 @@ def bin_events(ts, te, win_lo, win_hi):
     n, w = ts.numel(), lo.numel()
     if te.numel() != n or hi.numel() != w:
         raise ValueError("ts/te or window arrays differ in length")
-    sp = torch.empty(w, dtype=torch.int64, device=ts.device)
-    ex = torch.empty(w, dtype=torch.int64, device=ts.device)
-    br = torch.empty(w, dtype=torch.float64, device=ts.device)
+    sp = alloc_output(w, torch.int64, ts.device)
+    ex = alloc_output(w, torch.int64, ts.device)
+    br = alloc_output(w, torch.float64, ts.device)
     nbytes = lib.lr_bin_events_workspace_bytes(n, w)
     if nbytes < 0:
         _hip.check(int(nbytes), "lr_bin_events_workspace_bytes")
-    ws = _workspace(nbytes, ts.device)
+    ws = alloc_workspace(nbytes, ts.device, cached=True)
     rc = _hip.launch(lib.lr_bin_events, ts.device, _hip.ptr(ts), _hip.ptr(te), n, _hip.ptr(lo), _hip.ptr(hi), w, _hip.ptr(sp), _hip.ptr(ex),
                            _hip.ptr(br), _hip.ptr(ws), ws.numel())
     _hip.check(rc, "lr_bin_events")
@@ -138,7 +155,7 @@ def expand_rates(rates, times, K, n_bins, mode=0):
     C, kmax = rates.shape
     if times.shape != (C, kmax + 1) or K.shape != (C,):
         raise ValueError("shape mismatch: rates [C,kmax], times [C,kmax+1], K [C]")
-    out = torch.empty((C, n_bins), dtype=torch.float64, device=rates.device)
+    out = alloc_output((C, n_bins), torch.float64, rates.device)
     rc = _hip.launch(lib.lr_expand_rates, rates.device, _hip.ptr(rates), _hip.ptr(times), _hip.ptr(K), kmax, C, n_bins, mode, _hip.ptr(out))
     _hip.check(rc, "lr_expand_rates")
     return out
@@ -160,11 +177,11 @@ def bd_loglik_batch(ts, te, t0, lam_bins, mu_bins, model=2, br_length=None, end_
     br = None if br_length is None else _dev(br_length, torch.float64, ts.device)
     if br is not None and br.numel() != n_bins:
         raise ValueError("br_length must have n_bins entries")
-    out = torch.empty(C, dtype=torch.float64, device=ts.device)
+    out = alloc_output(C, torch.float64, ts.device)
     nbytes = lib.lr_bd_loglik_workspace_bytes(ts.numel(), n_bins, C, model)
     if nbytes < 0:
         _hip.check(int(nbytes), "lr_bd_loglik_workspace_bytes")
-    ws = _workspace(nbytes, ts.device)
+    ws = alloc_workspace(nbytes, ts.device, cached=True)
     rc = _hip.launch(lib.lr_bd_loglik_batch, ts.device, _hip.ptr(ts), _hip.ptr(te), ts.numel(), float(t0), n_bins, _hip.ptr(lam), _hip.ptr(mu),
                                 C, model, _hip.ptr(br), float(end_time), _hip.ptr(out), _hip.ptr(ws), ws.numel())
     _hip.check(rc, "lr_bd_loglik_batch")
@@ -206,9 +223,9 @@ def waic_pointwise(ts, te, t0, lam_bins, mu_bins, model=2, br_length=None, end_t
     if nbytes < 0:
         _hip.check(int(nbytes), "lr_waic_workspace_bytes")
     plan = waic_plan(n, n_bins, S, model)
-    pw = torch.empty((n, 3), dtype=torch.float64, device=ts.device)
-    tot = torch.empty(8, dtype=torch.float64, device=ts.device)
-    ws = _workspace(nbytes, ts.device)
+    pw = alloc_output((n, 3), torch.float64, ts.device)
+    tot = alloc_output(8, torch.float64, ts.device)
+    ws = alloc_workspace(nbytes, ts.device, cached=True)
     rc = _hip.launch(lib.lr_waic_pointwise, ts.device, _hip.ptr(ts), _hip.ptr(te), n, float(t0), n_bins, _hip.ptr(lam), _hip.ptr(mu),
                      S, int(model), _hip.ptr(br), float(end_time), _hip.ptr(pw), _hip.ptr(tot), _hip.ptr(ws), ws.numel())
     _hip.check(rc, "lr_waic_pointwise")
@@ -253,9 +270,9 @@ def loo_pointwise(ts, te, t0, lam_bins, mu_bins, model=2, br_length=None, end_ti
     if nbytes < 0:
         _hip.check(int(nbytes), "lr_loo_workspace_bytes")
     plan = loo_plan(n, n_bins, S, model)
-    pw = torch.empty((n, 4), dtype=torch.float64, device=ts.device)
-    tot = torch.empty(10, dtype=torch.float64, device=ts.device)
-    ws = _workspace(nbytes, ts.device)
+    pw = alloc_output((n, 4), torch.float64, ts.device)
+    tot = alloc_output(10, torch.float64, ts.device)
+    ws = alloc_workspace(nbytes, ts.device, cached=True)
     rc = _hip.launch(lib.lr_loo_pointwise, ts.device, _hip.ptr(ts), _hip.ptr(te), n, float(t0), n_bins, _hip.ptr(lam), _hip.ptr(mu),
                      S, int(model), _hip.ptr(br), float(end_time), _hip.ptr(pw), _hip.ptr(tot), _hip.ptr(ws), ws.numel())
     _hip.check(rc, "lr_loo_pointwise")
@@ -279,9 +296,9 @@ def psis_loo_rows(loglik, return_tail=False):
     nbytes = lib.lr_psis_rows_workspace_bytes(n, S)
     if nbytes < 0:
         _hip.check(int(nbytes), "lr_psis_rows_workspace_bytes")
-    pw = torch.empty((n, 4), dtype=torch.float64, device=L.device)
-    tot = torch.empty(10, dtype=torch.float64, device=L.device)
-    ws = _workspace(nbytes, L.device)
+    pw = alloc_output((n, 4), torch.float64, L.device)
+    tot = alloc_output(10, torch.float64, L.device)
+    ws = alloc_workspace(nbytes, L.device, cached=True)
     rc = _hip.launch(lib.lr_psis_rows, L.device, _hip.ptr(L), n, S, _hip.ptr(pw), _hip.ptr(tot), _hip.ptr(ws), ws.numel())
     _hip.check(rc, "lr_psis_rows")
     if return_tail:
@@ -317,13 +334,13 @@ class LoglikSession:
         if self.has_br:
             self.br_np[:] = _host_f64(br_length)
         self.stage = torch.empty_like(self.stage_host, device=dev)
-        self.out = torch.empty(self.C, dtype=torch.float64, device=dev)
+        self.out = alloc_output(self.C, torch.float64, dev)
         self.out_host = torch.empty(self.C, dtype=torch.float64).pin_memory()
         self.out_np = self.out_host.numpy()
         nbytes = self.lib.lr_bd_loglik_workspace_bytes(self.n, self.n_bins, self.C, self.model)
         if nbytes < 0:
             _hip.check(int(nbytes), "lr_bd_loglik_workspace_bytes")
-        self.ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)   # the session's own: nothing else scribbles on it
+        self.ws = alloc_workspace(int(nbytes), dev)   # the session's own: nothing else scribbles on it
         self.stream = torch.cuda.current_stream(dev)
         self.zero_copy = (self.C <= 16 and self.n <= (1 << 18) and self.n * self.C <= (1 << 21) and self.n_bins <= 900
                           and os.environ.get("LR_LOGLIK_SMALL", "1") != "0")
@@ -399,9 +416,9 @@ def rj_propose_score(rates, times, K, move, index, draws, mult_d=1.1):
     C, kmax = rates.shape
     if times.shape != (C, kmax + 1) or draws.shape != (C, 2 * kmax):
         raise ValueError("shape mismatch: times [C,kmax+1], draws [C,2*kmax]")
-    o_r, o_t = torch.empty_like(rates), torch.empty_like(times)
-    o_k = torch.empty_like(K)
-    o_s = torch.empty(C, dtype=torch.float64, device=rates.device)
+    o_r, o_t = alloc_output(rates.shape, rates.dtype, rates.device), alloc_output(times.shape, times.dtype, rates.device)
+    o_k = alloc_output(K.shape, K.dtype, rates.device)
+    o_s = alloc_output(C, torch.float64, rates.device)
     rc = _hip.launch(lib.lr_rj_propose_score, rates.device, _hip.ptr(rates), _hip.ptr(times), _hip.ptr(K), kmax, C, _hip.ptr(move), _hip.ptr(index),
                                  _hip.ptr(draws), float(mult_d), _hip.ptr(o_r), _hip.ptr(o_t), _hip.ptr(o_k),
                                  _hip.ptr(o_s))
@@ -420,7 +437,7 @@ def log_priors(rates, K, shape, gamma_rate, poi_rate=None):
     C, kmax = rates.shape
     g = _dev(gamma_rate, torch.float64)
     p = None if poi_rate is None else _dev(poi_rate, torch.float64)
-    out = torch.empty(C, dtype=torch.float64, device=rates.device)
+    out = alloc_output(C, torch.float64, rates.device)
     rc = _hip.launch(lib.lr_log_priors, rates.device, _hip.ptr(rates), _hip.ptr(K), kmax, C, float(shape), _hip.ptr(g), _hip.ptr(p), _hip.ptr(out))
     _hip.check(rc, "lr_log_priors")
     return out
@@ -436,7 +453,7 @@ def dd_rates(args, DT, m_birth=2, m_death=2):
     if args.shape[1] != 8:
         raise ValueError("DDRate takes 8 parameters per state")
     C, n_bins = args.shape[0], DT.numel()
-    outs = [torch.empty((C, n_bins), dtype=torch.float64, device=args.device) for _ in range(4)]
+    outs = [alloc_output((C, n_bins), torch.float64, args.device) for _ in range(4)]
     rc = _hip.launch(lib.lr_dd_rates, args.device, _hip.ptr(args), _hip.ptr(DT), n_bins, C, m_birth, m_death, *[_hip.ptr(o) for o in outs])
     _hip.check(rc, "lr_dd_rates")
     return tuple(outs)
@@ -452,7 +469,7 @@ def ddv2_rates(args, DT, m_birth=2, m_death=2):
     if args.shape[1] != 9:
         raise ValueError("DDRatev2 takes 9 parameters per state")
     C, n_bins = args.shape[0], DT.numel()
-    outs = [torch.empty((C, n_bins), dtype=torch.float64, device=args.device) for _ in range(4)]
+    outs = [alloc_output((C, n_bins), torch.float64, args.device) for _ in range(4)]
     rc = _hip.launch(lib.lr_ddv2_rates, args.device, _hip.ptr(args), _hip.ptr(DT), n_bins, C, m_birth, m_death, *[_hip.ptr(o) for o in outs])
     _hip.check(rc, "lr_ddv2_rates")
     return tuple(outs)
@@ -468,7 +485,7 @@ def trend_rates(args, trend, const_birth=False, const_death=False):
     if args.shape[1] != 6:
         raise ValueError("trend_rate takes 6 parameters per state")
     C, n_bins = args.shape[0], trend.numel()
-    outs = [torch.empty((C, n_bins), dtype=torch.float64, device=args.device) for _ in range(2)]
+    outs = [alloc_output((C, n_bins), torch.float64, args.device) for _ in range(2)]
     rc = _hip.launch(lib.lr_trend_rates, args.device, _hip.ptr(args), _hip.ptr(trend), n_bins, C, int(bool(const_birth)), int(bool(const_death)),
                             *[_hip.ptr(o) for o in outs])
     _hip.check(rc, "lr_trend_rates")
@@ -486,8 +503,8 @@ def binned_keiding(birth, death, n_spec, n_exti, DT):
     C, n_bins = birth.shape
     if death.shape != birth.shape or DT.numel() != n_bins or n_spec.numel() != n_bins or n_exti.numel() != n_bins:
         raise ValueError("shape mismatch")
-    ob = torch.empty(C, dtype=torch.float64, device=birth.device)
-    od = torch.empty_like(ob)
+    ob = alloc_output(C, torch.float64, birth.device)
+    od = alloc_output(C, torch.float64, birth.device)
     rc = _hip.launch(lib.lr_binned_keiding, birth.device, _hip.ptr(birth), _hip.ptr(death), _hip.ptr(n_spec), _hip.ptr(n_exti), _hip.ptr(DT),
                                n_bins, C, _hip.ptr(ob), _hip.ptr(od))
     _hip.check(rc, "lr_binned_keiding")
@@ -508,11 +525,11 @@ def simulate_bd(n_start, n_steps, seed, lam_steps=None, mu_steps=None, mode=0, l
     mu = None if mu_steps is None else _dev(mu_steps, torch.float64, dev)
     if mode == 0 and (lam is None or mu is None or lam.numel() < n_steps or mu.numel() < n_steps):
         raise ValueError("mode 0 needs lam_steps and mu_steps with n_steps entries")
-    ts = torch.empty(capacity, dtype=torch.float64, device=dev)
-    te = torch.empty(capacity, dtype=torch.float64, device=dev)
-    counters = torch.zeros(4, dtype=torch.int64, device=dev)
-    trace = torch.zeros(int(n_steps), dtype=torch.int64, device=dev)
-    ws = torch.zeros(64, dtype=torch.uint8, device=dev)
+    ts = alloc_output(capacity, torch.float64, dev)
+    te = alloc_output(capacity, torch.float64, dev)
+    counters = alloc_output(4, torch.int64, dev, zero=True)
+    trace = alloc_output(int(n_steps), torch.int64, dev, zero=True)
+    ws = alloc_workspace(64, dev, zero=True)
     rc = _hip.launch(lib.lr_simulate_bd, ts.device, _hip.ptr(lam), _hip.ptr(mu), int(n_steps), int(mode), float(l0), float(m0), float(K),
                             float(scale), int(n_start), capacity, int(seed) & 0xFFFFFFFFFFFFFFFF, _hip.ptr(ts), _hip.ptr(te),
                             _hip.ptr(counters), _hip.ptr(trace), _hip.ptr(ws), ws.numel())
@@ -550,9 +567,9 @@ def simulate_bd_batch(lam_bins, mu_bins, steps_per_bin, n_start, seed, capacity=
     nbytes = lib.lr_simulate_bd_batch_workspace_bytes(R, nb, int(steps_per_bin), capacity)
     if nbytes < 0:
         _hip.check(int(nbytes), "lr_simulate_bd_batch_workspace_bytes")
-    counts = torch.empty((R, 4, nb), dtype=torch.int64, device=dev)
-    totals = torch.empty((R, 4), dtype=torch.int64, device=dev)
-    ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
+    counts = alloc_output((R, 4, nb), torch.int64, dev)
+    totals = alloc_output((R, 4), torch.int64, dev)
+    ws = alloc_workspace(int(nbytes), dev)
     rc = _hip.launch(lib.lr_simulate_bd_batch, dev, _hip.ptr(lam), _hip.ptr(mu), R, nb, int(steps_per_bin), _hip.ptr(n0),
                      capacity, int(seed) & 0xFFFFFFFFFFFFFFFF, _hip.ptr(counts), _hip.ptr(totals), _hip.ptr(ws), ws.numel())
     _hip.check(rc, "lr_simulate_bd_batch")
@@ -593,9 +610,9 @@ def simulate_dd_batch(params, x_bins, steps_per_bin, n_start, seed, m_birth=2, m
     nbytes = lib.lr_simulate_dd_batch_workspace_bytes(R, nb, int(steps_per_bin), capacity)
     if nbytes < 0:
         _hip.check(int(nbytes), "lr_simulate_dd_batch_workspace_bytes")
-    counts = torch.empty((R, 4, nb), dtype=torch.int64, device=dev)
-    totals = torch.empty((R, 4), dtype=torch.int64, device=dev)
-    ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
+    counts = alloc_output((R, 4, nb), torch.int64, dev)
+    totals = alloc_output((R, 4), torch.int64, dev)
+    ws = alloc_workspace(int(nbytes), dev)
     rc = _hip.launch(lib.lr_simulate_dd_batch, dev, _hip.ptr(par), _hip.ptr(x), int(m_birth), int(m_death), R, nb,
                      int(steps_per_bin), _hip.ptr(n0), capacity, int(seed) & 0xFFFFFFFFFFFFFFFF, _hip.ptr(counts),
                      _hip.ptr(totals), _hip.ptr(ws), ws.numel())
@@ -637,9 +654,9 @@ def rtt_summary(trace, n_samples, start_age, end_age, burnin=0.2, pooled=True, w
     nb = time.size
     G = 1 if pooled else C
     dev = trace.device
-    rates = torch.empty((G, 3, 3, nb), dtype=torch.float64, device=dev)
-    freq = torch.empty((G, 2, nb), dtype=torch.float64, device=dev)
-    kc = torch.empty((G, 2, _hip.LR_KMAX), dtype=torch.int64, device=dev)
+    rates = alloc_output((G, 3, 3, nb), torch.float64, dev)
+    freq = alloc_output((G, 2, nb), torch.float64, dev)
+    kc = alloc_output((G, 2, _hip.LR_KMAX), torch.int64, dev)
     # by default at most a quarter of the free device memory (and never less than 1 GiB): the sort of a chunk's columns
     # runs a block per column, so the more columns a pass holds, the more CUs it keeps busy (a thousand chains pooled over
     # 123 bins: 7.3 GB in one pass)
@@ -649,7 +666,7 @@ def rtt_summary(trace, n_samples, start_age, end_age, burnin=0.2, pooled=True, w
         cap = int(os.environ["LR_RTT_WORKSPACE"])
     else:
         cap = max(1 << 30, torch.cuda.mem_get_info(dev)[0] // 4)
-    ws = torch.empty(max(1, min(int(full), cap)), dtype=torch.uint8, device=dev)
+    ws = alloc_workspace(max(1, min(int(full), cap)), dev)
     rc = _hip.launch(lib.lr_rtt_summary, dev, _hip.ptr(trace), S, C, a, b, float(burnin), int(bool(pooled)), _hip.ptr(rates),
                      _hip.ptr(freq), _hip.ptr(kc), _hip.ptr(ws), ws.numel())
     _hip.check(rc, "lr_rtt_summary")
@@ -680,9 +697,9 @@ def shift_prior(start_age, end_age, n_reps=1 << 20, seed=0, poi_lambda=None, rep
     if out is None:
         dev = "cuda"
         # (a span the library refuses still gets a histogram to point at: the refusal is the library's, LR_ERR_SIZE)
-        res = ShiftPrior(torch.empty(4, dtype=torch.int64, device=dev), torch.empty(max(nb, 1), dtype=torch.int64, device=dev),
-                         torch.empty(_hip.LR_SHIFT_PRIOR_KCAP, dtype=torch.int64, device=dev),
-                         torch.empty(_hip.LR_SHIFT_PRIOR_KCAP, dtype=torch.int64, device=dev))
+        res = ShiftPrior(alloc_output(4, torch.int64, dev), alloc_output(max(nb, 1), torch.int64, dev),
+                         alloc_output(_hip.LR_SHIFT_PRIOR_KCAP, torch.int64, dev),
+                         alloc_output(_hip.LR_SHIFT_PRIOR_KCAP, torch.int64, dev))
     else:
         res = out
         sizes = (4, nb, _hip.LR_SHIFT_PRIOR_KCAP, _hip.LR_SHIFT_PRIOR_KCAP)
@@ -719,10 +736,10 @@ def ess_summary(rows, n_samples, columns, burnin=0.1, max_lag=2000):
     if nbytes < 0:
         _hip.check(int(nbytes), "lr_ess_summary_workspace_bytes")
     dev = rows.device
-    cs = torch.empty((K, C, 4), dtype=torch.float64, device=dev)
-    stop = torch.empty((K, C), dtype=torch.int32, device=dev)
-    col = torch.empty((K, 3), dtype=torch.float64, device=dev)
-    ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
+    cs = alloc_output((K, C, 4), torch.float64, dev)
+    stop = alloc_output((K, C), torch.int32, dev)
+    col = alloc_output((K, 3), torch.float64, dev)
+    ws = alloc_workspace(int(nbytes), dev)
     rc = _hip.launch(lib.lr_ess_summary, dev, _hip.ptr(rows), S, C, W, cptr, K, float(burnin), int(max_lag), _hip.ptr(cs),
                      _hip.ptr(stop), _hip.ptr(col), _hip.ptr(ws), ws.numel())
     _hip.check(rc, "lr_ess_summary")
@@ -778,8 +795,8 @@ def col_summary(rows, n_samples, columns, burnin=0.2, pooled=True, workspace_byt
         _hip.check(int(full), "lr_col_summary_workspace_bytes")
     dev = rows.device
     G = 1 if pooled else C
-    out = torch.empty((G, K, 3), dtype=torch.float64, device=dev)
-    ws = torch.empty(max(1, min(int(full), _summary_cap(workspace_bytes, dev, torch))), dtype=torch.uint8, device=dev)
+    out = alloc_output((G, K, 3), torch.float64, dev)
+    ws = alloc_workspace(max(1, min(int(full), _summary_cap(workspace_bytes, dev, torch))), dev)
     rc = _hip.launch(lib.lr_col_summary, dev, _hip.ptr(rows), S, C, W, cptr, K, float(burnin), int(bool(pooled)),
                      _hip.ptr(out), _hip.ptr(ws), ws.numel())
     _hip.check(rc, "lr_col_summary")
@@ -808,8 +825,8 @@ def curve_summary(rows, n_samples, sampler, aux, m_birth, m_death, arg_col=4, bu
     dev = rows.device
     G = 1 if pooled else C
     kinds = CURVE_KINDS[sampler]
-    out = torch.empty((G, len(kinds), 3, nb), dtype=torch.float64, device=dev)
-    ws = torch.empty(max(1, min(int(full), _summary_cap(workspace_bytes, dev, torch))), dtype=torch.uint8, device=dev)
+    out = alloc_output((G, len(kinds), 3, nb), torch.float64, dev)
+    ws = alloc_workspace(max(1, min(int(full), _summary_cap(workspace_bytes, dev, torch))), dev)
     rc = _hip.launch(lib.lr_curve_summary, dev, _hip.ptr(rows), S, C, W, int(arg_col), sampler, int(m_birth), int(m_death),
                      _hip.ptr(aux), nb, float(burnin), int(bool(pooled)), _hip.ptr(out), _hip.ptr(ws), ws.numel())
     _hip.check(rc, "lr_curve_summary")
@@ -823,7 +840,7 @@ def debug_draws(seed, chain, it, purpose, idx, kind, shape):
     it = _dev(it, torch.int64)
     purpose, idx, kind = _dev(purpose, torch.int32), _dev(idx, torch.int32), _dev(kind, torch.int32)
     shape = _dev(shape, torch.float64)
-    out = torch.empty(it.numel(), dtype=torch.float64, device=it.device)
+    out = alloc_output(it.numel(), torch.float64, it.device)
     rc = _hip.launch(lib.lr_debug_draws, it.device, int(seed), int(chain), _hip.ptr(it), _hip.ptr(purpose), _hip.ptr(idx), _hip.ptr(kind),
                             _hip.ptr(shape), it.numel(), _hip.ptr(out))
     _hip.check(rc, "lr_debug_draws")
