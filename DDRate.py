@@ -161,11 +161,11 @@ def main(argv=None):
         write_run_ppc_dd(eng, n_local, args.chains, world, rank, args.ppc, args.ppc_draws, args.ppc_scale, seed, stem,
                          start_bin=args.ppc_start_bin if args.ppc_start_bin >= 0 else None)
     if args.waic != -1.0 and n_samples:
-        from literate_amd.waic import write_run_waic_dd
-        write_run_waic_dd(eng, n_local, args.chains, world, rank, args.waic, args.waic_draws, stem)
+        from literate_amd import waic
+        waic.write_run(eng, n_local, args.chains, world, rank, args.waic, args.waic_draws, stem)
     if args.loo != -1.0 and n_samples:
-        from literate_amd.loo import write_run_loo_dd
-        write_run_loo_dd(eng, n_local, args.chains, world, rank, args.loo, args.loo_draws, stem)
+        from literate_amd import loo
+        loo.write_run(eng, n_local, args.chains, world, rank, args.loo, args.loo_draws, stem)
     eng.close()
     if world > 1:
         dist.barrier()

@@ -286,11 +286,11 @@ def main(argv=None):
     if args.waic != -1.0 and n_samples:
         from literate_amd import waic
         stem = logs.log_paths(args.d, args.model_BDI, args.out)[1]["div"][:-len("_div.log")]
-        waic.write_run_waic(eng, n_local, args.chains, world, rank, args.waic, args.waic_draws, stem)
+        waic.write_run(eng, n_local, args.chains, world, rank, args.waic, args.waic_draws, stem)
     if args.loo != -1.0 and n_samples:
         from literate_amd import loo
         stem = logs.log_paths(args.d, args.model_BDI, args.out)[1]["div"][:-len("_div.log")]
-        loo.write_run_loo(eng, n_local, args.chains, world, rank, args.loo, args.loo_draws, stem)
+        loo.write_run(eng, n_local, args.chains, world, rank, args.loo, args.loo_draws, stem)
     eng.close()
     if world > 1:
         dist.destroy_process_group()

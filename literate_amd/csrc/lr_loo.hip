@@ -5,8 +5,8 @@
 // WAIC (lr_waic.hip) needs running moments over a lineage's draws and never stores a term.  PSIS needs ORDER statistics:
 // the M largest importance ratios of every lineage in sorted order.  So the work is two stages per batch of lineages:
 //
-//   lr_loo_terms_kernel   the walk of lr_waic_kernel (a tile of lineages, the draws' tables through LDS chunk by chunk, the
-//                         next chunk prefetched), but the term is STORED: a batch of B lineages gives a [B, S] row-major
+//   lr_loo_terms_kernel   the walk WAIC takes (lr_walk_draws, csrc/lr_drawwalk.h: a tile of lineages, the draws' tables
+//                         through LDS), but the term is STORED: a batch of B lineages gives a [B, S] row-major
 //                         slab in the workspace (at most 64 MiB; the host loops over the batches); grid.y slices the
 //                         draws, since a batch alone is too few tiles to fill the device
 //   lr_psis_rows_kernel   one workgroup per row: the row's S terms go to LDS as keys r = -l with their draw indices, a
@@ -27,17 +27,9 @@
 #include <climits>
 #include <cstdlib>
 
-#include "lr_device.h"
-#include "lr_internal.h"
+#include "lr_drawwalk.h"
 
-#define LR_LOO_THREADS 256                               /* terms kernel: the shape of lr_waic_kernel */
-#define LR_LOO_LPT 2
-#define LR_LOO_TILE (LR_LOO_THREADS * LR_LOO_LPT)
-#define LR_LOO_PF 8
-#define LR_LOO_LDS_HALF (32 * 1024)
-#define LR_LOO_LDS_ONE (152 * 1024)
 #define LR_LOO_SLAB_BYTES (64ll * 1024 * 1024)
-#define LR_LOO_BLOCKS 512                                /* blocks of the terms kernel aimed at: two per CU */
 #define LR_LOO_MAX_DRAWS 8192
 #define LR_PSIS_MAX_THREADS 256
 #define LR_PSIS_MAX_TAIL 272                             /* ceil(3 sqrt(8192)) */
@@ -45,9 +37,7 @@
 #define LR_LOO_TOT_THREADS 1024
 
 struct lr_loo_shape {
-    int n_cls, H, tab_stride;
-    int chunk, nbuf;
-    size_t lds_bytes;
+    lr_draw_shape w;
     long long batch;     // lineages per batch
     int batches;
 };
@@ -63,93 +53,32 @@ struct lr_psis_shape {
 // ------------------------------------------------------------------------------------------
 // stage 1: the terms
 // ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(LR_LOO_THREADS) void lr_loo_terms_kernel(
+// the walk's sink: row[k] is lineage slot k's row of the slab (null past the end)
+struct lr_loo_sink {
+    double* row[LR_DRAW_LPT];
+    __device__ __forceinline__ void operator()(int k, int d, double l) const {
+        if (row[k]) row[k][d] = l;
+    }
+};
+
+__global__ __launch_bounds__(LR_DRAW_THREADS) void lr_loo_terms_kernel(
     const double* __restrict__ ts, const double* __restrict__ te, long long n, double t0, int n_bins, int n_cls, int H,
     double end_time, const double2* __restrict__ tables, int tab_stride, int n_draws, int chunk, int nbuf, int dps,
     double* __restrict__ slab) {
-    extern __shared__ double2 lds[];
-    const int tid = threadIdx.x;
-    const long long first = (long long)blockIdx.x * LR_LOO_TILE;
+    const long long first = (long long)blockIdx.x * LR_DRAW_TILE;
     const int d0 = blockIdx.y * dps, d1 = min(d0 + dps, n_draws);     // this block's slice of the draws (no state crosses draws)
-    const double nb1 = (double)(n_bins + 1);
-
-    double s[LR_LOO_LPT], e[LR_LOO_LPT];
-    bool valid[LR_LOO_LPT];
-    double* row[LR_LOO_LPT];
+    lr_loo_sink sink;
 #pragma unroll
-    for (int k = 0; k < LR_LOO_LPT; ++k) {
-        const long long i = first + k * LR_LOO_THREADS + tid;
-        valid[k] = i < n;
-        s[k] = valid[k] ? ts[i] : 0.0;      // (a lane past the end scores a lineage of its own: indices stay in the table)
-        e[k] = valid[k] ? te[i] : 0.0;
-        row[k] = slab + (size_t)(valid[k] ? i : 0) * (size_t)n_draws;
+    for (int k = 0; k < LR_DRAW_LPT; ++k) {
+        const long long i = first + k * LR_DRAW_THREADS + threadIdx.x;
+        sink.row[k] = i < n ? slab + (size_t)i * (size_t)n_draws : nullptr;
     }
-
-    const int chunk_entries = chunk * tab_stride;
-    {
-        const double2* src = tables + (size_t)d0 * tab_stride;
-        const int nent = min(chunk, d1 - d0) * tab_stride;
-        for (int i = tid; i < nent; i += LR_LOO_THREADS) lds[i] = src[i];
-    }
-    __syncthreads();
-    int cur = 0;
-    for (int dc = d0; dc < d1; dc += chunk) {
-        const int nd = min(chunk, d1 - dc);
-        const int nx = dc + chunk;
-        const int nent = nx < d1 ? min(chunk, d1 - nx) * tab_stride : 0;
-        const double2* nsrc = tables + (size_t)nx * tab_stride;
-        double2 r[LR_LOO_PF];
-#pragma unroll
-        for (int q = 0; q < LR_LOO_PF; ++q) {
-            const int idx = q * LR_LOO_THREADS + tid;
-            r[q] = idx < nent ? nsrc[idx] : make_double2(0.0, 0.0);
-        }
-        const double2* buf = lds + (size_t)cur * chunk_entries;
-        for (int d = 0; d < nd; ++d) {
-#pragma unroll
-            for (int k = 0; k < LR_LOO_LPT; ++k) {
-                double acc[1] = {0.0};
-                lr_score_lineage<1>(s[k], e[k], t0, nb1, H, n_cls, end_time, buf + (size_t)d * tab_stride, tab_stride, acc);
-                if (valid[k]) row[k][dc + d] = acc[0];
-            }
-        }
-        if (nbuf == 1) __syncthreads();
-        double2* dst = lds + (size_t)(nbuf == 2 ? (cur ^ 1) : 0) * chunk_entries;
-#pragma unroll
-        for (int q = 0; q < LR_LOO_PF; ++q) {
-            const int idx = q * LR_LOO_THREADS + tid;
-            if (idx < nent) dst[idx] = r[q];
-        }
-        for (int idx = LR_LOO_PF * LR_LOO_THREADS + tid; idx < nent; idx += LR_LOO_THREADS) dst[idx] = nsrc[idx];
-        __syncthreads();
-        if (nbuf == 2) cur ^= 1;
-    }
+    lr_walk_draws(ts, te, n, first, t0, n_bins, n_cls, H, end_time, tables, tab_stride, d0, d1, chunk, nbuf, sink);
 }
 
 // ------------------------------------------------------------------------------------------
 // stage 2: one row per workgroup
 // ------------------------------------------------------------------------------------------
-// block sum in a fixed order (lanes by the DPP scan, then the waves in ascending order); every thread gets it
-__device__ __forceinline__ double lr_psis_block_sum(double v, double* red, int tid, int nw) {
-    const double w = lr_wave_sum(v);
-    __syncthreads();
-    if ((tid & (LR_WAVE - 1)) == 0) red[tid / LR_WAVE] = w;
-    __syncthreads();
-    double t = 0.0;
-    for (int k = 0; k < nw; ++k) t += red[k];
-    return t;
-}
-
-__device__ __forceinline__ double lr_psis_block_max(double v, double* red, int tid, int nw) {
-    const double w = -lr_wave_min(-v);
-    __syncthreads();
-    if ((tid & (LR_WAVE - 1)) == 0) red[tid / LR_WAVE] = w;
-    __syncthreads();
-    double t = red[0];
-    for (int k = 1; k < nw; ++k) t = fmax(t, red[k]);
-    return t;
-}
-
 __device__ __forceinline__ bool lr_psis_finite(double v) { return fabs(v) < __builtin_inf(); }
 
 // out_pointwise[4 row ...] = elpd_loo, pareto_k, lppd, n_eff; tails (may be null): [n_rows, M] draw indices of the tail in
@@ -213,7 +142,7 @@ __global__ __launch_bounds__(LR_PSIS_MAX_THREADS) void lr_psis_rows_kernel(const
     // lppd = max l + log(1/S sum exp(l - max l)), max l = -rmin
     double acc = 0.0;
     for (int s = lo + tid; s < P; s += T) acc += exp(rmin - keys[s]);
-    const double lppd = -rmin + log(lr_psis_block_sum(acc, red, tid, nw) / (double)S);
+    const double lppd = -rmin + log(lr_block_sum(acc, red, tid, nw) / (double)S);
 
     const double c = keys[t_at - 1];                     // the largest r not in the tail (M = 0: rmax itself)
     const double ec = exp(c - rmax);
@@ -267,8 +196,8 @@ __global__ __launch_bounds__(LR_PSIS_MAX_THREADS) void lr_psis_rows_kernel(const
         mA = fmax(mA, lw - keys[s]);
         mB = fmax(mB, lw);
     }
-    mA = lr_psis_block_max(mA, red, tid, nw);
-    mB = lr_psis_block_max(mB, red, tid, nw);
+    mA = lr_block_max(mA, red, tid, nw);
+    mB = lr_block_max(mB, red, tid, nw);
     double sA = 0.0, sB = 0.0, s2 = 0.0;
     for (int s = lo + tid; s < P; s += T) {
         const double lw = (smoothed && s >= t_at) ? x[s - t_at] : keys[s] - rmax;
@@ -277,9 +206,9 @@ __global__ __launch_bounds__(LR_PSIS_MAX_THREADS) void lr_psis_rows_kernel(const
         sB += w;
         s2 += w * w;
     }
-    sA = lr_psis_block_sum(sA, red, tid, nw);
-    sB = lr_psis_block_sum(sB, red, tid, nw);
-    s2 = lr_psis_block_sum(s2, red, tid, nw);
+    sA = lr_block_sum(sA, red, tid, nw);
+    sB = lr_block_sum(sB, red, tid, nw);
+    s2 = lr_block_sum(s2, red, tid, nw);
     if (tid == 0) {
         out[0] = (mA - mB) + log(sA / sB);               // logsumexp(l + lw) - logsumexp(lw)
         out[1] = k_rep;
@@ -289,24 +218,9 @@ __global__ __launch_bounds__(LR_PSIS_MAX_THREADS) void lr_psis_rows_kernel(const
 }
 
 // ------------------------------------------------------------------------------------------
-// totals: thread j takes rows j, j + 1024, ... in ascending order; the 1024 sums are added 32 by 32, the 32 by every
-// thread in ascending order.  The standard error is two passes (the mean, then the squares about it).
+// totals: thread j takes rows j, j + 1024, ... in ascending order; the 1024 sums are added by lr_ordered_sum.  The
+// standard error is two passes (the mean, then the squares about it).
 // ------------------------------------------------------------------------------------------
-__device__ __forceinline__ double lr_loo_ordered_sum(double v, double* red, int j) {
-    __syncthreads();
-    red[j] = v;
-    __syncthreads();
-    if (j < 32) {
-        double t = 0.0;
-        for (int q = 0; q < 32; ++q) t += red[j * 32 + q];
-        red[LR_LOO_TOT_THREADS + j] = t;
-    }
-    __syncthreads();
-    double t = 0.0;
-    for (int q = 0; q < 32; ++q) t += red[LR_LOO_TOT_THREADS + q];
-    return t;
-}
-
 __global__ __launch_bounds__(LR_LOO_TOT_THREADS) void lr_loo_totals_kernel(const double* __restrict__ pw, long long n,
                                                                            double* __restrict__ out_totals) {
     __shared__ double red[LR_LOO_TOT_THREADS + 32];
@@ -329,7 +243,7 @@ __global__ __launch_bounds__(LR_LOO_TOT_THREADS) void lr_loo_totals_kernel(const
         }
     }
     double tot[8];
-    for (int q = 0; q < 8; ++q) tot[q] = lr_loo_ordered_sum(a[q], red, j);
+    for (int q = 0; q < 8; ++q) tot[q] = lr_ordered_sum<LR_LOO_TOT_THREADS>(a[q], red, j);
     __syncthreads();
     red[j] = kmax;
     __syncthreads();
@@ -342,7 +256,7 @@ __global__ __launch_bounds__(LR_LOO_TOT_THREADS) void lr_loo_totals_kernel(const
         const double elpd = pw[4 * i], lppd = pw[4 * i + 2];
         if (lppd == lppd) m2 += (elpd - mean) * (elpd - mean);
     }
-    m2 = lr_loo_ordered_sum(m2, red, j);
+    m2 = lr_ordered_sum<LR_LOO_TOT_THREADS>(m2, red, j);
     if (j == 0) {
         const bool any = used > 0.0;
         out_totals[0] = used, out_totals[1] = tot[1];
@@ -420,31 +334,16 @@ extern "C" int lr_psis_rows(const double* loglik, int64_t n_rows, int32_t n_draw
 
 static int lr_loo_shape_of(long long n, int n_bins, int n_draws, int model, lr_loo_shape* p, lr_psis_shape* q) {
     if (n < 1 || n_draws < 2 || n_draws > LR_LOO_MAX_DRAWS) return LR_ERR_SIZE;
-    if (model != LR_MODEL_BD && model != LR_MODEL_KEIDING && model != LR_MODEL_KEIDING_DEAD) return LR_ERR_MODEL;
-    lr_scan_plan sp;                                   // the bin counts lr_bd_loglik_batch accepts, by its own planner
-    int rc = lr_plan_scan(n, n_draws, n_bins, model, 0, &sp, 1);
+    const int rc = lr_draw_shape_of(n, n_bins, n_draws, model, &p->w);
     if (rc != LR_OK) return rc;
-    p->n_cls = sp.n_cls;
-    p->H = n_bins + 2;
-    p->tab_stride = p->n_cls * 2 * p->H;
-    const size_t per_draw = (size_t)p->tab_stride * sizeof(double2);
-    if (per_draw <= LR_LOO_LDS_HALF) {
-        p->chunk = (int)(LR_LOO_LDS_HALF / per_draw), p->nbuf = 2;
-    } else if (2 * per_draw <= LR_LOO_LDS_ONE) {
-        p->chunk = 1, p->nbuf = 2;
-    } else {
-        if (per_draw > LR_LOO_LDS_ONE) return LR_ERR_SIZE;
-        p->chunk = 1, p->nbuf = 1;
-    }
-    p->lds_bytes = per_draw * p->chunk * p->nbuf;
     // lineages per batch: the slab of terms stays within 64 MiB (whole tiles when the lineages do not fit one slab)
     long long B = LR_LOO_SLAB_BYTES / (8ll * n_draws);
     if (B >= n) B = n;
-    else B = B / LR_LOO_TILE * LR_LOO_TILE;
+    else B = B / LR_DRAW_TILE * LR_DRAW_TILE;
     const char* env = getenv("LR_LOO_BATCH");
     if (env && atoll(env) > 0) B = atoll(env) < n ? atoll(env) : n;
     const long long batches = (n + B - 1) / B;
-    if (batches > INT_MAX || (B + LR_LOO_TILE - 1) / LR_LOO_TILE > INT_MAX) return LR_ERR_SIZE;
+    if (batches > INT_MAX || (B + LR_DRAW_TILE - 1) / LR_DRAW_TILE > INT_MAX) return LR_ERR_SIZE;
     p->batch = B, p->batches = (int)batches;
     return lr_psis_shape_of(B, n_draws, q);
 }
@@ -454,7 +353,7 @@ static int lr_loo_shape_of(long long n, int n_bins, int n_draws, int model, lr_l
 static void lr_loo_ws(const lr_loo_shape& p, int n_draws, size_t* o_slab, size_t* o_tab, size_t* o_cst, size_t* total) {
     size_t o = 0;
     *o_slab = o, o += lr_align_up64(p.batch * (long long)n_draws * (long long)sizeof(double), 256);
-    *o_tab = o, o += lr_align_up64((long long)n_draws * p.tab_stride * sizeof(double2), 256);
+    *o_tab = o, o += lr_align_up64((long long)n_draws * p.w.tab_stride * sizeof(double2), 256);
     *o_cst = o, o += lr_align_up64((long long)n_draws * sizeof(double), 256);
     *total = o;
 }
@@ -489,41 +388,25 @@ extern "C" int lr_loo_pointwise(const double* ts, const double* te, int64_t n, d
     lr_psis_shape q;
     int rc = lr_loo_shape_of(n, n_bins, n_draws, model, &p, &q);
     if (rc != LR_OK) return rc;
-    if (model == LR_MODEL_BD && !br_length) return LR_ERR_MODEL;
-    if (t0 != floor(t0)) return LR_ERR_T0;
     size_t o_slab, o_tab, o_cst, total;
     lr_loo_ws(p, n_draws, &o_slab, &o_tab, &o_cst, &total);
-    if ((int64_t)total > workspace_bytes) return LR_ERR_WORKSPACE;
     hipStream_t stream = (hipStream_t)stream_;
+    rc = lr_draw_begin(p.w, model, br_length, t0, total, workspace, workspace_bytes, o_tab, o_cst, lam_bins, mu_bins, n_bins,
+                       n_draws, reinterpret_cast<const void*>(&lr_loo_terms_kernel), stream);
+    if (rc) return rc;
     char* ws = (char*)workspace;
     double* slab = (double*)(ws + o_slab);
-    double2* tables = (double2*)(ws + o_tab);
-    double* consts = (double*)(ws + o_cst);      // (zero under models 0, 2 and 3: nothing of the likelihood lies outside the lineages)
-    rc = lr_launch_build_tables(lam_bins, mu_bins, br_length, model, n_bins, p.n_cls, p.H, p.tab_stride, n_draws, tables,
-                                consts, stream);
-    if (rc) return rc;
-    if (p.lds_bytes > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&lr_loo_terms_kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes);
-        if (e != hipSuccess) return (int)e;
-    }
+    const double2* tables = (const double2*)(ws + o_tab);
     for (long long start = 0; start < n; start += p.batch) {
         const long long cnt = n - start < p.batch ? n - start : p.batch;
-        const int tiles = (int)((cnt + LR_LOO_TILE - 1) / LR_LOO_TILE);
-        // a batch is few tiles (16 at 1000 draws): slices of draws along grid.y until two blocks per CU exist, each slice
-        // at least two chunks long.  Every term is computed as before, whatever the slice it falls into.
-        int slices = 1;
-        if (tiles < LR_LOO_BLOCKS) {
-            slices = (LR_LOO_BLOCKS + tiles - 1) / tiles;
-            const int most = n_draws / (2 * p.chunk);
-            if (slices > most) slices = most;
-            if (slices < 1) slices = 1;
-        }
-        const int dps = (n_draws + slices - 1) / slices;
-        slices = (n_draws + dps - 1) / dps;
-        hipLaunchKernelGGL(lr_loo_terms_kernel, dim3(tiles, slices), dim3(LR_LOO_THREADS), p.lds_bytes, stream, ts + start,
-                           te + start, cnt, t0, n_bins, p.n_cls, p.H, end_time, tables, p.tab_stride, n_draws, p.chunk, p.nbuf,
-                           dps, slab);
+        const int tiles = (int)((cnt + LR_DRAW_TILE - 1) / LR_DRAW_TILE);
+        // a batch is few tiles (16 at 1000 draws): grid.y slices the draws.  Every term is computed as before, whatever the
+        // slice it falls into.
+        int slices, dps;
+        lr_draw_slices(tiles, n_draws, p.w.chunk, 0, &slices, &dps);
+        hipLaunchKernelGGL(lr_loo_terms_kernel, dim3(tiles, slices), dim3(LR_DRAW_THREADS), p.w.lds_bytes, stream, ts + start,
+                           te + start, cnt, t0, n_bins, p.w.n_cls, p.w.H, end_time, tables, p.w.tab_stride, n_draws, p.w.chunk,
+                           p.w.nbuf, dps, slab);
         rc = (int)hipGetLastError();
         if (rc) return rc;
         rc = lr_psis_launch(q, slab, cnt, n_draws, out_pointwise + 4 * start, nullptr, stream);

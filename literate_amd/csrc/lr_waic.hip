@@ -1,12 +1,8 @@
 // lr_waic.hip - pointwise WAIC over posterior draws: the lineage scan with the terms kept apart per lineage.
 //
-// lr_scan_kernel (lr_loglik.hip) sums lr_score_lineage's term over the lineages of a tile, per chain.  Here a block owns
-// a tile of lineages and walks the DRAWS: a thread holds its lineages' times in registers (the index rule of
-// lr_score_lineage depends on them alone, so the compiler keeps js / je / fs / fe and the table class out of the draw
-// loop), the tables lr_build_tables_kernel made of a chunk of draws sit in LDS, and the next chunk travels from L2 into
-// registers while the current one is scored.  Every (lineage, draw) is two 16-byte LDS gathers, the four fp64
-// operations of the term, one exponential (running maximum with a rescaled sum) and a Welford update.  Nothing of the
-// [lineages, draws] matrix is ever stored.
+// A block owns a tile of lineages and walks the draws (lr_walk_draws, csrc/lr_drawwalk.h: the tables of a chunk of draws in
+// LDS, the next chunk prefetched); the sink folds every term into the lineage's running state: one exponential (running
+// maximum with a rescaled sum) and a Welford update.  Nothing of the [lineages, draws] matrix is ever stored.
 //
 //   lr_waic_kernel         grid (tiles, slices): per lineage and draw slice the state (max, rescaled sum, mean, M2, flag);
 //                          with ONE slice it finishes the lineage and writes the tile's partial totals itself
@@ -18,28 +14,17 @@
 #include <climits>
 #include <cstdlib>
 
-#include "lr_device.h"
-#include "lr_internal.h"
+#include "lr_drawwalk.h"
 
-#define LR_WAIC_THREADS 256
-#define LR_WAIC_LPT 2                                    /* lineages per thread */
-#define LR_WAIC_TILE (LR_WAIC_THREADS * LR_WAIC_LPT)
-#define LR_WAIC_PF 8                                     /* double2 per thread of the next chunk held in registers */
-#define LR_WAIC_LDS_HALF (32 * 1024)                     /* one of the two chunk buffers when two blocks share a CU */
-#define LR_WAIC_LDS_ONE (152 * 1024)                     /* both buffers of a block that has the CU to itself */
-#define LR_WAIC_BLOCKS 512                               /* blocks aimed at: two per CU */
 #define LR_WAIC_NSTATE 5                                 /* max, sum, mean, M2, flag */
 #define LR_WAIC_NPART 8                                  /* used, flagged, lppd, var, elpd, n(var > 0.4), max var, M2 of elpd */
 #define LR_WAIC_VAR_WARN 0.4
 
 struct lr_waic_shape {
-    int n_cls, H, tab_stride;
-    int chunk;      // draws per LDS buffer
-    int nbuf;       // 2: the next chunk lands in the other buffer; 1: a table takes most of the LDS, one buffer
+    lr_draw_shape w;
     int slices;     // draw slices (grid.y)
     int dps;        // draws per slice
     int tiles;      // lineage tiles (grid.x)
-    size_t lds_bytes;
 };
 
 struct lr_waic_state {
@@ -75,33 +60,20 @@ __device__ __forceinline__ void lr_waic_merge(lr_waic_state& a, double na, const
     a.M2 = (a.M2 + b.M2) + (delta * delta) * (na * nb / nt);
 }
 
-__device__ __forceinline__ double lr_waic_wave_max(double v) { return -lr_wave_min(-v); }
-
-// block sum in a fixed order (lanes by the DPP scan, then the waves in ascending order); every thread gets it
-__device__ __forceinline__ double lr_waic_block_sum(double v, double* red, int tid) {
-    const double w = lr_wave_sum(v);
-    __syncthreads();
-    if ((tid & (LR_WAVE - 1)) == 0) red[tid / LR_WAVE] = w;
-    __syncthreads();
-    double t = 0.0;
-#pragma unroll
-    for (int k = 0; k < LR_WAIC_THREADS / LR_WAVE; ++k) t += red[k];
-    return t;
-}
-
 // The finished lineages of a tile: the three outputs per lineage (NaN where flagged) and the tile's partial totals,
 // tile_part[q * tiles + tile].  All threads of the block call.
-__device__ __forceinline__ void lr_waic_emit(const lr_waic_state (&st)[LR_WAIC_LPT], const bool (&valid)[LR_WAIC_LPT],
+__device__ __forceinline__ void lr_waic_emit(const lr_waic_state (&st)[LR_DRAW_LPT], const bool (&valid)[LR_DRAW_LPT],
                                              long long first, long long n, double n_draws, int tile, int tiles, int tid,
                                              double* __restrict__ out_pointwise, double* __restrict__ tile_part) {
-    __shared__ double red[LR_WAIC_THREADS / LR_WAVE];
+    constexpr int NW = LR_DRAW_THREADS / LR_WAVE;
+    __shared__ double red[NW];
     const double nan = __builtin_nan("");
     double used = 0.0, flagged = 0.0, s_lppd = 0.0, s_var = 0.0, s_elpd = 0.0, n_gt = 0.0, vmax = -__builtin_inf();
-    double elpd[LR_WAIC_LPT];
-    bool use[LR_WAIC_LPT];
+    double elpd[LR_DRAW_LPT];
+    bool use[LR_DRAW_LPT];
 #pragma unroll
-    for (int k = 0; k < LR_WAIC_LPT; ++k) {
-        const long long i = first + k * LR_WAIC_THREADS + tid;
+    for (int k = 0; k < LR_DRAW_LPT; ++k) {
+        const long long i = first + k * LR_DRAW_THREADS + tid;
         double lppd = st[k].m + lr_log(st[k].sum / n_draws);
         double mean = st[k].mean;
         double var = st[k].M2 / (n_draws - 1.0);
@@ -121,107 +93,67 @@ __device__ __forceinline__ void lr_waic_emit(const lr_waic_state (&st)[LR_WAIC_L
         }
     }
     (void)n;
-    used = lr_waic_block_sum(used, red, tid);
-    flagged = lr_waic_block_sum(flagged, red, tid);
-    s_lppd = lr_waic_block_sum(s_lppd, red, tid);
-    s_var = lr_waic_block_sum(s_var, red, tid);
-    s_elpd = lr_waic_block_sum(s_elpd, red, tid);
-    n_gt = lr_waic_block_sum(n_gt, red, tid);
+    used = lr_block_sum(used, red, tid, NW);
+    flagged = lr_block_sum(flagged, red, tid, NW);
+    s_lppd = lr_block_sum(s_lppd, red, tid, NW);
+    s_var = lr_block_sum(s_var, red, tid, NW);
+    s_elpd = lr_block_sum(s_elpd, red, tid, NW);
+    n_gt = lr_block_sum(n_gt, red, tid, NW);
     // the tile's sum of squares about ITS mean: the totals kernel joins the tiles as Chan et al. join samples
     const double tmean = used > 0.0 ? s_elpd / used : 0.0;
     double m2 = 0.0;
 #pragma unroll
-    for (int k = 0; k < LR_WAIC_LPT; ++k)
+    for (int k = 0; k < LR_DRAW_LPT; ++k)
         if (use[k]) m2 += (elpd[k] - tmean) * (elpd[k] - tmean);
-    m2 = lr_waic_block_sum(m2, red, tid);
-    const double wmax = lr_waic_wave_max(vmax);
-    __syncthreads();
-    if ((tid & (LR_WAVE - 1)) == 0) red[tid / LR_WAVE] = wmax;
-    __syncthreads();
+    m2 = lr_block_sum(m2, red, tid, NW);
+    vmax = lr_block_max(vmax, red, tid, NW);
     if (tid == 0) {
-        double t = red[0];
-#pragma unroll
-        for (int k = 1; k < LR_WAIC_THREADS / LR_WAVE; ++k) t = fmax(t, red[k]);
         const size_t T = (size_t)tiles;
         tile_part[0 * T + tile] = used, tile_part[1 * T + tile] = flagged, tile_part[2 * T + tile] = s_lppd;
         tile_part[3 * T + tile] = s_var, tile_part[4 * T + tile] = s_elpd, tile_part[5 * T + tile] = n_gt;
-        tile_part[6 * T + tile] = t, tile_part[7 * T + tile] = m2;
+        tile_part[6 * T + tile] = vmax, tile_part[7 * T + tile] = m2;
     }
 }
 
+// the walk's sink: draw d of the slice that starts at d0 is the (d - d0 + 1)-th of the lineage's state.  The state is
+// updated in a copy: updated in place through the reference, the allocator keeps the running maximum twice in the draw
+// loop (112 VGPRs for 108, three more instructions per draw in the loop that ends a chunk).
+struct lr_waic_sink {
+    lr_waic_state (&st)[LR_DRAW_LPT];
+    int d0;
+    __device__ __forceinline__ void operator()(int k, int d, double l) const {
+        lr_waic_state t = st[k];
+        lr_waic_update(t, l, 1.0 / (double)(d - d0 + 1));
+        st[k] = t;
+    }
+};
+
 // state[(q * slices + slice) * n + i]: field q of lineage i in draw slice `slice`
-__global__ __launch_bounds__(LR_WAIC_THREADS) void lr_waic_kernel(
+__global__ __launch_bounds__(LR_DRAW_THREADS) void lr_waic_kernel(
     const double* __restrict__ ts, const double* __restrict__ te, long long n, double t0, int n_bins, int n_cls, int H,
     double end_time, const double2* __restrict__ tables, int tab_stride, int n_draws, int chunk, int nbuf, int dps, int slices,
     double* __restrict__ out_pointwise, double* __restrict__ state, double* __restrict__ tile_part) {
-    extern __shared__ double2 lds[];
     const int tid = threadIdx.x, tile = blockIdx.x, slice = blockIdx.y;
     const int d0 = slice * dps, d1 = min(d0 + dps, n_draws);
-    const long long first = (long long)tile * LR_WAIC_TILE;
-    const double nb1 = (double)(n_bins + 1);
+    const long long first = (long long)tile * LR_DRAW_TILE;
 
-    double s[LR_WAIC_LPT], e[LR_WAIC_LPT];
-    bool valid[LR_WAIC_LPT];
-    lr_waic_state st[LR_WAIC_LPT];
+    bool valid[LR_DRAW_LPT];
+    lr_waic_state st[LR_DRAW_LPT];
 #pragma unroll
-    for (int k = 0; k < LR_WAIC_LPT; ++k) {
-        const long long i = first + k * LR_WAIC_THREADS + tid;
-        valid[k] = i < n;
-        s[k] = valid[k] ? ts[i] : 0.0;      // (a lane past the end scores a lineage of its own: indices stay in the table)
-        e[k] = valid[k] ? te[i] : 0.0;
+    for (int k = 0; k < LR_DRAW_LPT; ++k) {
+        valid[k] = first + k * LR_DRAW_THREADS + tid < n;
         st[k].m = -__builtin_inf(), st[k].sum = 0.0, st[k].mean = 0.0, st[k].M2 = 0.0, st[k].bad = 0;
     }
-
-    const int chunk_entries = chunk * tab_stride;
-    {
-        const double2* src = tables + (size_t)d0 * tab_stride;
-        const int nent = min(chunk, d1 - d0) * tab_stride;
-        for (int i = tid; i < nent; i += LR_WAIC_THREADS) lds[i] = src[i];
-    }
-    __syncthreads();
-    int cur = 0, cnt = 0;
-    for (int dc = d0; dc < d1; dc += chunk) {
-        const int nd = min(chunk, d1 - dc);
-        const int nx = dc + chunk;
-        const int nent = nx < d1 ? min(chunk, d1 - nx) * tab_stride : 0;
-        const double2* nsrc = tables + (size_t)nx * tab_stride;
-        // the next chunk's first LR_WAIC_PF * 256 entries (all of it when two blocks share a CU) travel while this one is scored
-        double2 r[LR_WAIC_PF];
-#pragma unroll
-        for (int q = 0; q < LR_WAIC_PF; ++q) {
-            const int idx = q * LR_WAIC_THREADS + tid;
-            r[q] = idx < nent ? nsrc[idx] : make_double2(0.0, 0.0);
-        }
-        const double2* buf = lds + (size_t)cur * chunk_entries;
-        for (int d = 0; d < nd; ++d) {
-            ++cnt;
-            const double inv = 1.0 / (double)cnt;
-#pragma unroll
-            for (int k = 0; k < LR_WAIC_LPT; ++k) {
-                double acc[1] = {0.0};
-                lr_score_lineage<1>(s[k], e[k], t0, nb1, H, n_cls, end_time, buf + (size_t)d * tab_stride, tab_stride, acc);
-                lr_waic_update(st[k], acc[0], inv);
-            }
-        }
-        if (nbuf == 1) __syncthreads();     // one buffer: everybody is done with it before it is overwritten
-        double2* dst = lds + (size_t)(nbuf == 2 ? (cur ^ 1) : 0) * chunk_entries;
-#pragma unroll
-        for (int q = 0; q < LR_WAIC_PF; ++q) {
-            const int idx = q * LR_WAIC_THREADS + tid;
-            if (idx < nent) dst[idx] = r[q];
-        }
-        for (int idx = LR_WAIC_PF * LR_WAIC_THREADS + tid; idx < nent; idx += LR_WAIC_THREADS) dst[idx] = nsrc[idx];
-        __syncthreads();
-        if (nbuf == 2) cur ^= 1;
-    }
+    lr_walk_draws(ts, te, n, first, t0, n_bins, n_cls, H, end_time, tables, tab_stride, d0, d1, chunk, nbuf,
+                  lr_waic_sink{st, d0});
 
     if (slices == 1) {
         lr_waic_emit(st, valid, first, n, (double)n_draws, tile, gridDim.x, tid, out_pointwise, tile_part);
         return;
     }
 #pragma unroll
-    for (int k = 0; k < LR_WAIC_LPT; ++k) {
-        const long long i = first + k * LR_WAIC_THREADS + tid;
+    for (int k = 0; k < LR_DRAW_LPT; ++k) {
+        const long long i = first + k * LR_DRAW_THREADS + tid;
         if (!valid[k]) continue;
         const size_t plane = (size_t)slices * n, o = (size_t)slice * n + i;
         state[o] = st[k].m, state[plane + o] = st[k].sum, state[2 * plane + o] = st[k].mean, state[3 * plane + o] = st[k].M2;
@@ -229,18 +161,18 @@ __global__ __launch_bounds__(LR_WAIC_THREADS) void lr_waic_kernel(
     }
 }
 
-__global__ __launch_bounds__(LR_WAIC_THREADS) void lr_waic_merge_kernel(const double* __restrict__ state, long long n,
+__global__ __launch_bounds__(LR_DRAW_THREADS) void lr_waic_merge_kernel(const double* __restrict__ state, long long n,
                                                                         int n_draws, int dps, int slices,
                                                                         double* __restrict__ out_pointwise,
                                                                         double* __restrict__ tile_part) {
     const int tid = threadIdx.x, tile = blockIdx.x;
-    const long long first = (long long)tile * LR_WAIC_TILE;
+    const long long first = (long long)tile * LR_DRAW_TILE;
     const size_t plane = (size_t)slices * n;
-    bool valid[LR_WAIC_LPT];
-    lr_waic_state st[LR_WAIC_LPT];
+    bool valid[LR_DRAW_LPT];
+    lr_waic_state st[LR_DRAW_LPT];
 #pragma unroll
-    for (int k = 0; k < LR_WAIC_LPT; ++k) {
-        const long long i = first + k * LR_WAIC_THREADS + tid;
+    for (int k = 0; k < LR_DRAW_LPT; ++k) {
+        const long long i = first + k * LR_DRAW_THREADS + tid;
         valid[k] = i < n;
         st[k].m = 0.0, st[k].sum = 1.0, st[k].mean = 0.0, st[k].M2 = 0.0, st[k].bad = 0;
         if (!valid[k]) continue;
@@ -260,24 +192,7 @@ __global__ __launch_bounds__(LR_WAIC_THREADS) void lr_waic_merge_kernel(const do
 }
 
 // out_totals[8] from the tile partials: thread j adds tiles j, j + 256, ... in ascending order, the 256 sums are then
-// added 16 by 16 and the 16 by thread 0 - the order of lr_reduce_partials_kernel
-__device__ __forceinline__ double lr_waic_ordered_sum(double v, double* red, int j) {
-    __syncthreads();
-    red[j] = v;
-    __syncthreads();
-    if (j < 16) {
-        double t = 0.0;
-#pragma unroll
-        for (int q = 0; q < 16; ++q) t += red[j * 16 + q];
-        red[256 + j] = t;
-    }
-    __syncthreads();
-    double t = 0.0;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) t += red[256 + q];
-    return t;
-}
-
+// added by lr_ordered_sum
 __global__ __launch_bounds__(256) void lr_waic_totals_kernel(const double* __restrict__ tile_part, int tiles,
                                                              double* __restrict__ out_totals) {
     __shared__ double red[256 + 16];
@@ -292,7 +207,7 @@ __global__ __launch_bounds__(256) void lr_waic_totals_kernel(const double* __res
     }
     double tot[6];
 #pragma unroll
-    for (int q = 0; q < 6; ++q) tot[q] = lr_waic_ordered_sum(acc[q], red, j);
+    for (int q = 0; q < 6; ++q) tot[q] = lr_ordered_sum<256>(acc[q], red, j);
     __syncthreads();
     red[j] = vmax;
     __syncthreads();
@@ -308,7 +223,7 @@ __global__ __launch_bounds__(256) void lr_waic_totals_kernel(const double* __res
             m2 += tile_part[7 * T + k] + u * (dm * dm);
         }
     }
-    m2 = lr_waic_ordered_sum(m2, red, j);
+    m2 = lr_ordered_sum<256>(m2, red, j);
     if (j == 0) {
         const double nan = __builtin_nan("");
         out_totals[0] = used, out_totals[1] = tot[1], out_totals[2] = tot[2], out_totals[3] = tot[3], out_totals[4] = tot[4];
@@ -323,40 +238,13 @@ __global__ __launch_bounds__(256) void lr_waic_totals_kernel(const double* __res
 // ------------------------------------------------------------------------------------------
 static int lr_waic_shape_of(long long n, int n_bins, int n_draws, int model, lr_waic_shape* p) {
     if (n < 1 || n_draws < 2) return LR_ERR_SIZE;
-    if (model != LR_MODEL_BD && model != LR_MODEL_KEIDING && model != LR_MODEL_KEIDING_DEAD) return LR_ERR_MODEL;
-    lr_scan_plan sp;                                   // the bin counts lr_bd_loglik_batch accepts, by its own planner
-    const int rc = lr_plan_scan(n, n_draws, n_bins, model, 0, &sp, 1);
+    const int rc = lr_draw_shape_of(n, n_bins, n_draws, model, &p->w);
     if (rc != LR_OK) return rc;
-    const long long tiles = (n + LR_WAIC_TILE - 1) / LR_WAIC_TILE;
+    const long long tiles = (n + LR_DRAW_TILE - 1) / LR_DRAW_TILE;
     if (tiles > INT_MAX) return LR_ERR_SIZE;
-    p->n_cls = sp.n_cls;
-    p->H = n_bins + 2;
-    p->tab_stride = p->n_cls * 2 * p->H;
-    const size_t per_draw = (size_t)p->tab_stride * sizeof(double2);
-    if (per_draw <= LR_WAIC_LDS_HALF) {
-        p->chunk = (int)(LR_WAIC_LDS_HALF / per_draw), p->nbuf = 2;
-    } else if (2 * per_draw <= LR_WAIC_LDS_ONE) {
-        p->chunk = 1, p->nbuf = 2;
-    } else {
-        if (per_draw > LR_WAIC_LDS_ONE) return LR_ERR_SIZE;
-        p->chunk = 1, p->nbuf = 1;
-    }
-    p->lds_bytes = per_draw * p->chunk * p->nbuf;
     p->tiles = (int)tiles;
-    // few lineages: slices of draws along grid.y until two blocks per CU exist, each slice at least two chunks long
-    int slices = 1;
-    if (tiles < LR_WAIC_BLOCKS) {
-        slices = (int)((LR_WAIC_BLOCKS + tiles - 1) / tiles);
-        const int most = n_draws / (2 * p->chunk);
-        if (slices > most) slices = most;
-    }
     const char* env = getenv("LR_WAIC_SLICES");
-    if (env && atoi(env) > 0) slices = atoi(env);
-    if (slices > n_draws) slices = n_draws;
-    if (slices > 65535) slices = 65535;
-    if (slices < 1) slices = 1;
-    p->dps = (n_draws + slices - 1) / slices;
-    p->slices = (n_draws + p->dps - 1) / p->dps;
+    lr_draw_slices(tiles, n_draws, p->w.chunk, env ? atoi(env) : 0, &p->slices, &p->dps);
     return LR_OK;
 }
 
@@ -364,7 +252,7 @@ static int lr_waic_shape_of(long long n, int n_bins, int n_draws, int model, lr_
 static void lr_waic_ws(const lr_waic_shape& p, long long n, int n_draws, size_t* o_tab, size_t* o_cst, size_t* o_part,
                        size_t* o_state, size_t* total) {
     size_t o = 0;
-    *o_tab = o, o += lr_align_up64((long long)n_draws * p.tab_stride * sizeof(double2), 256);
+    *o_tab = o, o += lr_align_up64((long long)n_draws * p.w.tab_stride * sizeof(double2), 256);
     *o_cst = o, o += lr_align_up64((long long)n_draws * sizeof(double), 256);
     *o_part = o, o += lr_align_up64((long long)p.tiles * LR_WAIC_NPART * sizeof(double), 256);
     *o_state = o;
@@ -386,7 +274,7 @@ extern "C" int lr_waic_plan(int64_t n, int32_t n_bins, int32_t n_draws, int32_t 
     lr_waic_shape p;
     const int rc = lr_waic_shape_of(n, n_bins, n_draws, model, &p);
     if (rc != LR_OK) return rc;
-    out[0] = LR_WAIC_TILE, out[1] = p.chunk, out[2] = p.slices, out[3] = p.tiles;
+    out[0] = LR_DRAW_TILE, out[1] = p.w.chunk, out[2] = p.slices, out[3] = p.tiles;
     return LR_OK;
 }
 
@@ -398,33 +286,23 @@ extern "C" int lr_waic_pointwise(const double* ts, const double* te, int64_t n, 
     lr_waic_shape p;
     int rc = lr_waic_shape_of(n, n_bins, n_draws, model, &p);
     if (rc != LR_OK) return rc;
-    if (model == LR_MODEL_BD && !br_length) return LR_ERR_MODEL;
-    if (t0 != floor(t0)) return LR_ERR_T0;
     size_t o_tab, o_cst, o_part, o_state, total;
     lr_waic_ws(p, n, n_draws, &o_tab, &o_cst, &o_part, &o_state, &total);
-    if ((int64_t)total > workspace_bytes) return LR_ERR_WORKSPACE;
     hipStream_t stream = (hipStream_t)stream_;
+    rc = lr_draw_begin(p.w, model, br_length, t0, total, workspace, workspace_bytes, o_tab, o_cst, lam_bins, mu_bins, n_bins,
+                       n_draws, reinterpret_cast<const void*>(&lr_waic_kernel), stream);
+    if (rc) return rc;
     char* ws = (char*)workspace;
-    double2* tables = (double2*)(ws + o_tab);
-    double* consts = (double*)(ws + o_cst);      // (zero under models 0, 2 and 3: nothing of the likelihood lies outside the lineages)
+    const double2* tables = (const double2*)(ws + o_tab);
     double* tile_part = (double*)(ws + o_part);
     double* state = (double*)(ws + o_state);
-    rc = lr_launch_build_tables(lam_bins, mu_bins, br_length, model, n_bins, p.n_cls, p.H, p.tab_stride, n_draws, tables,
-                                consts, stream);
-    if (rc) return rc;
-    if (p.lds_bytes > 64 * 1024) {
-        // (per call: the attribute belongs to the function on the CURRENT device, and a process may drive several)
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&lr_waic_kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes);
-        if (e != hipSuccess) return (int)e;
-    }
-    hipLaunchKernelGGL(lr_waic_kernel, dim3(p.tiles, p.slices), dim3(LR_WAIC_THREADS), p.lds_bytes, stream, ts, te,
-                       (long long)n, t0, n_bins, p.n_cls, p.H, end_time, tables, p.tab_stride, n_draws, p.chunk, p.nbuf, p.dps,
-                       p.slices, out_pointwise, state, tile_part);
+    hipLaunchKernelGGL(lr_waic_kernel, dim3(p.tiles, p.slices), dim3(LR_DRAW_THREADS), p.w.lds_bytes, stream, ts, te,
+                       (long long)n, t0, n_bins, p.w.n_cls, p.w.H, end_time, tables, p.w.tab_stride, n_draws, p.w.chunk,
+                       p.w.nbuf, p.dps, p.slices, out_pointwise, state, tile_part);
     rc = (int)hipGetLastError();
     if (rc) return rc;
     if (p.slices > 1) {
-        hipLaunchKernelGGL(lr_waic_merge_kernel, dim3(p.tiles), dim3(LR_WAIC_THREADS), 0, stream, state, (long long)n, n_draws,
+        hipLaunchKernelGGL(lr_waic_merge_kernel, dim3(p.tiles), dim3(LR_DRAW_THREADS), 0, stream, state, (long long)n, n_draws,
                            p.dps, p.slices, out_pointwise, tile_part);
         rc = (int)hipGetLastError();
         if (rc) return rc;

@@ -68,6 +68,14 @@ class DDRateEngine(ChainEngine):
                 O[:, 14 + 4 * n:] = logs.adequacy_rows(emp[0], emp[1], b, d)
         return out.reshape(lead + (out.shape[1],))
 
+    def draw_rates(self, flat_rows, idx):
+        """per-bin rates (lam_bins, mu_bins) [R, n_bins] of rows idx of the flat trace rows (device): ops.dd_rates of their
+        columns 4:12 at the observed DT (the log's l_i / m_i columns)"""
+        from . import ppc
+        import torch
+        par = flat_rows[torch.as_tensor(idx, device=flat_rows.device)][:, 4:12].contiguous()
+        return ppc.chunked_rates(lambda q: ops.dd_rates(q, self.DT, self.m_birth, self.m_death), par)
+
     def ess_rows(self, rows):
         """The trace rows' first 12 columns (it, posterior, likelihood, prior, args[8]) with midpoint_x0 and maxCarryingCap
         formed on the device as log_table_from forms them (x0 + ORIGIN, L + div_0): the values as the log holds them."""

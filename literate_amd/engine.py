@@ -449,6 +449,12 @@ class ChainEngine:
         return ops.rtt_summary(self.trace, self.samples_done(), self.cfg.start_time, self.cfg.end_time, burnin, pooled,
                                workspace_bytes)
 
+    def draw_rates(self, flat_rows, idx):
+        """per-bin rates (lam_bins, mu_bins) [R, n_bins] of rows idx of the flat trace rows (device): what --ppc, --waic and
+        --loo score.  The RJ skylines expanded to the bins (ppc.draw_rates); DDRate and trend_rate have their own."""
+        from . import ppc
+        return ppc.draw_rates(flat_rows, idx, self.n_bins)
+
     def ess_rows(self, rows):
         """Trace rows [S, C, LR_TRACE_W] -> (rows whose columns hold the log's values as the log holds them, the indices of
         the sampler's diagnosable columns there, the names of the rows' leading columns).  runMCMC logs its trace head

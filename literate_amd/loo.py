@@ -48,13 +48,11 @@ lineages per batch, batches); draw_rows: the trace rows the draws came from (Non
 
 def arg_error(burnin, n_draws, model=2, pyrate_output=False, rm_first_bin=False):
     """Why a CLI's --loo BURNIN cannot run (None when it can): waic.arg_error's rules, and --loo_draws in [2, 8192]."""
-    err = waic.arg_error(burnin, n_draws, model=model, pyrate_output=pyrate_output, rm_first_bin=rm_first_bin)
-    if err:
-        return err.replace("--waic_draws must be at least 2 (a variance over the draws)",
-                           "--loo_draws must lie in [2, %d]" % MAX_DRAWS).replace("--waic", "--loo")
-    if n_draws > MAX_DRAWS:
+    err = waic._arg_error("--loo", "--loo_draws must lie in [2, %d]" % MAX_DRAWS, burnin, n_draws, model, pyrate_output,
+                          rm_first_bin)
+    if err is None and n_draws > MAX_DRAWS:
         return "--loo_draws must lie in [2, %d] (a lineage's draws are sorted in the GPU's local memory)" % MAX_DRAWS
-    return None
+    return err
 
 
 def loo_from_rates(ts, te, t0, lam_bins, mu_bins, model=2, br_length=None, end_time=0.0, draw_rows=None):
@@ -69,153 +67,56 @@ def loo_from_rates(ts, te, t0, lam_bins, mu_bins, model=2, br_length=None, end_t
                      pw[:, 0].copy(), pw[:, 1].copy(), pw, fp, plan, draw_rows)
 
 
-def _drawn(rows, n_draws):
-    if n_draws > MAX_DRAWS:
-        raise ValueError("PSIS-LOO takes at most %d draws" % MAX_DRAWS)
-    return waic._drawn(rows, n_draws)
-
-
-def _score(eng, lam, mu, idx):
-    return loo_from_rates(eng.ts, eng.te, eng.t0, lam, mu, model=eng.model,
-                          br_length=eng.br_length if eng.model == 0 else None, end_time=eng.end_time, draw_rows=idx)
-
-
-def loo_of_rows(eng, rows, n_draws):
-    """LiteRateForward's engine: the drawn rows' per-bin rates by ppc.draw_rates, scored on the engine's lineages"""
-    from . import ppc
-    flat, idx, _ = _drawn(rows, n_draws)
-    lam, mu = ppc.draw_rates(flat, idx, eng.n_bins)
-    return _score(eng, lam, mu, idx)
-
-
-def loo_of_rows_dd(eng, rows, n_draws):
-    """DDRate's engine: ops.dd_rates of the drawn rows' columns 4:12 at the observed DT (at most 8192 draws: one launch)"""
-    from . import ops
-    flat, idx, torch = _drawn(rows, n_draws)
-    par = flat[torch.as_tensor(idx, device=flat.device)][:, 4:12].contiguous()
-    lam, mu = ops.dd_rates(par, eng.DT, eng.m_birth, eng.m_death)[:2]
-    return _score(eng, lam, mu, idx)
-
-
-def loo_of_rows_trend(eng, rows, n_draws):
-    """trend_rate's engine: ops.trend_rates of the drawn rows' columns 4:10"""
-    from . import ops
-    flat, idx, torch = _drawn(rows, n_draws)
-    par = flat[torch.as_tensor(idx, device=flat.device)][:, 4:10].contiguous()
-    lam, mu = ops.trend_rates(par, eng.trend, eng.const_birth, eng.const_death)
-    return _score(eng, lam, mu, idx)
-
-
 def write_files(stem, res):
     """<stem>_LOO.tsv (TSV_HEAD, one row; numbers as str(float), counts as integers) and <stem>_LOO_pointwise.npz (elpd [n]
     and pareto_k [n] in the order of the scored lineages, NaN where flagged; fingerprint [6]; method = "psis-loo")."""
-    vals = [res.draws, res.lineages, res.lineages_used, res.lineages_flagged, res.elpd_loo, res.se_elpd, res.p_loo, res.lppd,
-            res.looic, res.se_looic, res.n_k_gt_05, res.n_k_gt_07, res.n_unsmoothed, res.max_k]
-    with open(stem + "_LOO.tsv", "w") as f:
-        f.write("\t".join(TSV_HEAD) + "\n")
-        f.write("\t".join("%d" % v if k in TSV_INTS else str(float(v)) for k, v in zip(TSV_HEAD, vals)) + "\n")
+    waic._write_row(stem + "_LOO.tsv", TSV_HEAD, TSV_INTS,
+                    [res.draws, res.lineages, res.lineages_used, res.lineages_flagged, res.elpd_loo, res.se_elpd, res.p_loo,
+                     res.lppd, res.looic, res.se_looic, res.n_k_gt_05, res.n_k_gt_07, res.n_unsmoothed, res.max_k])
     np.savez(stem + "_LOO_pointwise.npz", elpd=np.asarray(res.elpd, dtype=np.float64),
              pareto_k=np.asarray(res.pareto_k, dtype=np.float64), fingerprint=res.fingerprint, method=np.array(METHOD))
 
 
-def _write_and_say(stem, res):
-    write_files(stem, res)
-    print("LOO: %s_LOO.tsv, %s_LOO_pointwise.npz (%d draws, %d lineages, %d flagged; elpd_loo %.6f, se %.6f, p_loo %.6f; "
-          "%d lineages with k > 0.7)" % (stem, stem, res.draws, res.lineages, res.lineages_flagged, res.elpd_loo, res.se_elpd,
-                                         res.p_loo, res.n_k_gt_07))
-    return res
+def _say(stem, res):
+    return ("LOO: %s_LOO.tsv, %s_LOO_pointwise.npz (%d draws, %d lineages, %d flagged; elpd_loo %.6f, se %.6f, p_loo %.6f; "
+            "%d lineages with k > 0.7)" % (stem, stem, res.draws, res.lineages, res.lineages_flagged, res.elpd_loo, res.se_elpd,
+                                           res.p_loo, res.n_k_gt_07))
 
 
-def _run(of_rows, eng, n_local, total_chains, world, rank, burnin, n_draws, stem):
-    from . import ppc
-    rows = ppc._gathered_rows(eng, n_local, total_chains, world, burnin)     # (every rank calls: a collective)
-    if rank != 0:
-        return None
-    return _write_and_say(stem, of_rows(eng, rows, n_draws))
-
-
-def write_run_loo(eng, n_local, total_chains, world, rank, burnin, n_draws, stem):
-    """LiteRateForward.py's --loo: the rows the run sampled, int(burnin * S) dropped per chain, gathered to rank 0 and
-    scored against the engine's own lineages, window, model id and br_length -> the two files and one line on stdout."""
-    return _run(loo_of_rows, eng, n_local, total_chains, world, rank, burnin, n_draws, stem)
-
-
-def write_run_loo_dd(eng, n_local, total_chains, world, rank, burnin, n_draws, stem):
-    """DDRate.py's --loo (rates: ops.dd_rates at the observed DT, the log's l_i / m_i columns)."""
-    return _run(loo_of_rows_dd, eng, n_local, total_chains, world, rank, burnin, n_draws, stem)
-
-
-def write_run_loo_trend(eng, n_local, total_chains, world, rank, burnin, n_draws, stem):
-    """trend_rate.py's --loo (rates: ops.trend_rates of the drawn parameters)."""
-    return _run(loo_of_rows_trend, eng, n_local, total_chains, world, rank, burnin, n_draws, stem)
+def write_run(eng, n_local, total_chains, world, rank, burnin, n_draws, stem):
+    """The three CLIs' --loo (waic._run with loo_from_rates): <stem>_LOO.tsv, <stem>_LOO_pointwise.npz, one line on stdout."""
+    return waic._run(loo_from_rates, write_files, _say, eng, n_local, total_chains, world, rank, burnin, n_draws, stem,
+                     cap=(MAX_DRAWS, "PSIS-LOO takes at most %d draws" % MAX_DRAWS))
 
 
 # ------------------------------------------------------------------------------------------------
 # comparison of pointwise files (host only)
 # ------------------------------------------------------------------------------------------------
-def _beside(path, name):
-    """column `name` of the <stem>_LOO.tsv that write_files left beside <stem>_LOO_pointwise.npz (nan when it is not there)"""
-    import os
-    tsv = path[:-len("_pointwise.npz")] + ".tsv" if path.endswith("_pointwise.npz") else None
-    if not tsv or not os.path.exists(tsv):
-        return float("nan")
-    with open(tsv) as f:
-        head, row = f.readline().rstrip("\n").split("\t"), f.readline().rstrip("\n").split("\t")
-    return float(row[head.index(name)]) if name in head and len(row) == len(head) else float("nan")
+def _read(p, z):
+    if "method" not in z.files or str(z["method"]) != METHOD:
+        raise ValueError("%s is not a PSIS-LOO pointwise file (method=\"%s\"): WAIC and LOO values are not "
+                         "comparable with each other" % (p, METHOD))
+    k = np.asarray(z["pareto_k"], dtype=np.float64) if "pareto_k" in z.files else None
+    return np.asarray(z["elpd"], dtype=np.float64), np.asarray(z["fingerprint"], dtype=np.float64), k
 
 
 def compare(paths):
     """Two or more <stem>_LOO_pointwise.npz -> rows sorted by elpd_loo, best first (waic.compare_arrays' arithmetic, with
     p_loo and the number of lineages with k > 0.7 per run); ValueError for a file that is not a PSIS-LOO file and unless
     every file's fingerprint equals the first one's."""
-    paths = list(paths)
-    if len(paths) < 2:
-        raise ValueError("compare takes two or more pointwise files")
-    loaded = []
-    for p in paths:
-        with np.load(p) as z:
-            if "method" not in z.files or str(z["method"]) != METHOD:
-                raise ValueError("%s is not a PSIS-LOO pointwise file (method=\"%s\"): WAIC and LOO values are not "
-                                 "comparable with each other" % (p, METHOD))
-            k = np.asarray(z["pareto_k"], dtype=np.float64) if "pareto_k" in z.files else None
-            loaded.append((np.asarray(z["elpd"], dtype=np.float64), np.asarray(z["fingerprint"], dtype=np.float64), k))
-    for p, (e, fp, _) in zip(paths[1:], loaded[1:]):
-        bad = fingerprint_mismatch(loaded[0][1], fp)
-        if bad is None and len(e) != len(loaded[0][0]):
-            bad = "n"
-        if bad:
-            raise ValueError("fingerprint mismatch (%s): %s and %s were not scored on the same lineages, window and model id; "
-                             "their WAIC values are not comparable" % (bad, paths[0], p))
-    rows = waic.compare_arrays(paths, [e for e, _, _ in loaded], [_beside(p, "p_loo") for p in paths])
+    paths, loaded = waic._comparable(paths, _read)
+    rows = waic.compare_arrays(paths, [e for e, _, _ in loaded], [waic._beside(p, "p_loo") for p in paths])
     n_bad = {p: (-1 if k is None else int(np.sum(np.isfinite(k) & (k > 0.7)))) for p, (_, _, k) in zip(paths, loaded)}
     return [{"model": r["model"], "elpd_loo": r["elpd_waic"], "p_loo": r["p_waic"], "elpd_diff": r["elpd_diff"],
              "se_diff": r["se_diff"], "lineages_used": r["lineages_used"], "n_k_gt_0.7": n_bad[r["model"]]} for r in rows]
 
 
 def format_table(rows):
-    lines = ["\t".join(COMPARE_HEAD)]
-    for r in rows:
-        lines.append("\t".join([str(r["model"])] + [str(float(r[k])) for k in COMPARE_HEAD[1:5]] +
-                               ["%d" % r["lineages_used"], "%d" % r["n_k_gt_0.7"]]))
-    return "\n".join(lines) + "\n"
+    return waic._format_rows(COMPARE_HEAD, rows)
 
 
 def main(argv=None):
-    import argparse
-    p = argparse.ArgumentParser(prog="python -m literate_amd.loo",
-                                description="rank runs by PSIS-LOO from their <stem>_LOO_pointwise.npz files")
-    p.add_argument("files", nargs="+", help="two or more <stem>_LOO_pointwise.npz written by --loo")
-    p.add_argument("-o", default="", help="also write the table to this file")
-    args = p.parse_args(argv)
-    try:
-        text = format_table(compare(args.files))
-    except ValueError as ex:
-        raise SystemExit(str(ex))
-    print(text, end="")
-    if args.o:
-        with open(args.o, "w") as f:
-            f.write(text)
-    return 0
+    return waic._main(argv, "loo", "PSIS-LOO", "LOO", compare, format_table)
 
 
 if __name__ == "__main__":

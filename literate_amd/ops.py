@@ -202,13 +202,11 @@ def waic_plan(n, n_bins, n_draws, model=2):
     return tuple(int(v) for v in out)
 
 
-def waic_pointwise(ts, te, t0, lam_bins, mu_bins, model=2, br_length=None, end_time=0.0):
-    """Pointwise WAIC terms of S posterior draws of per-bin rates [S, n_bins] (lr_waic_pointwise): returns
-    (pointwise [n, 3] = lppd_i, mean_i, var_i - NaN where a lineage's term is not finite under some draw -,
-    totals [8] (WAIC_TOTALS), plan (WAIC_PLAN, host tuple)), tensors on the device.  The [n, S] matrix of terms is never
-    stored.  Models 0, 2 and 3."""
+def _draws_pointwise(workspace_bytes, plan_of, pointwise, width, n_totals, ts, te, t0, lam_bins, mu_bins, model, br_length,
+                     end_time):
+    """waic_pointwise / loo_pointwise around their three entry points: the arguments on the device and checked, the plan, the
+    outputs [n, width] and [n_totals], the cached workspace, the launch -> (pointwise, totals, plan, workspace, n, S)"""
     torch = _torch()
-    lib = _hip.load()
     ts = _dev(ts, torch.float64)
     te = _dev(te, torch.float64, ts.device)
     lam, mu = _dev(lam_bins, torch.float64, ts.device), _dev(mu_bins, torch.float64, ts.device)
@@ -219,17 +217,27 @@ def waic_pointwise(ts, te, t0, lam_bins, mu_bins, model=2, br_length=None, end_t
     br = None if br_length is None else _dev(br_length, torch.float64, ts.device)
     if br is not None and br.numel() != n_bins:
         raise ValueError("br_length must have n_bins entries")
-    nbytes = lib.lr_waic_workspace_bytes(n, n_bins, S, int(model))
+    nbytes = workspace_bytes(n, n_bins, S, int(model))
     if nbytes < 0:
-        _hip.check(int(nbytes), "lr_waic_workspace_bytes")
-    plan = waic_plan(n, n_bins, S, model)
-    pw = alloc_output((n, 3), torch.float64, ts.device)
-    tot = alloc_output(8, torch.float64, ts.device)
+        _hip.check(int(nbytes), workspace_bytes.__name__)
+    plan = plan_of(n, n_bins, S, model)
+    pw = alloc_output((n, width), torch.float64, ts.device)
+    tot = alloc_output(n_totals, torch.float64, ts.device)
     ws = alloc_workspace(nbytes, ts.device, cached=True)
-    rc = _hip.launch(lib.lr_waic_pointwise, ts.device, _hip.ptr(ts), _hip.ptr(te), n, float(t0), n_bins, _hip.ptr(lam), _hip.ptr(mu),
-                     S, int(model), _hip.ptr(br), float(end_time), _hip.ptr(pw), _hip.ptr(tot), _hip.ptr(ws), ws.numel())
-    _hip.check(rc, "lr_waic_pointwise")
-    return pw, tot, plan
+    rc = _hip.launch(pointwise, ts.device, _hip.ptr(ts), _hip.ptr(te), n, float(t0), n_bins, _hip.ptr(lam), _hip.ptr(mu), S,
+                     int(model), _hip.ptr(br), float(end_time), _hip.ptr(pw), _hip.ptr(tot), _hip.ptr(ws), ws.numel())
+    _hip.check(rc, pointwise.__name__)
+    return pw, tot, plan, ws, n, S
+
+
+def waic_pointwise(ts, te, t0, lam_bins, mu_bins, model=2, br_length=None, end_time=0.0):
+    """Pointwise WAIC terms of S posterior draws of per-bin rates [S, n_bins] (lr_waic_pointwise): returns
+    (pointwise [n, 3] = lppd_i, mean_i, var_i - NaN where a lineage's term is not finite under some draw -,
+    totals [8] (WAIC_TOTALS), plan (WAIC_PLAN, host tuple)), tensors on the device.  The [n, S] matrix of terms is never
+    stored.  Models 0, 2 and 3."""
+    lib = _hip.load()
+    return _draws_pointwise(lib.lr_waic_workspace_bytes, waic_plan, lib.lr_waic_pointwise, 3, 8, ts, te, t0, lam_bins, mu_bins,
+                            model, br_length, end_time)[:3]
 
 
 LOO_TOTALS = ("lineages_used", "lineages_flagged", "elpd_loo", "se_elpd", "p_loo", "lppd", "n_k_gt_0.5", "n_k_gt_0.7",
@@ -254,32 +262,13 @@ def loo_pointwise(ts, te, t0, lam_bins, mu_bins, model=2, br_length=None, end_ti
     elpd_loo_i, pareto_k_i, lppd_i, n_eff_i - NaN where a lineage's term is not finite under some draw -, totals [10]
     (LOO_TOTALS), plan (LOO_PLAN, host tuple)), tensors on the device.  Models 0, 2 and 3; 2 <= S <= 8192.
     return_terms (a test hook; one batch only): also a copy of the [n, S] matrix of terms the first stage wrote."""
-    torch = _torch()
     lib = _hip.load()
-    ts = _dev(ts, torch.float64)
-    te = _dev(te, torch.float64, ts.device)
-    lam, mu = _dev(lam_bins, torch.float64, ts.device), _dev(mu_bins, torch.float64, ts.device)
-    if lam.dim() != 2 or mu.shape != lam.shape or te.numel() != ts.numel() or ts.dim() != 1:
-        raise ValueError("shape mismatch: ts, te [n]; lam_bins, mu_bins [draws, n_bins]")
-    S, n_bins = lam.shape
-    n = ts.numel()
-    br = None if br_length is None else _dev(br_length, torch.float64, ts.device)
-    if br is not None and br.numel() != n_bins:
-        raise ValueError("br_length must have n_bins entries")
-    nbytes = lib.lr_loo_workspace_bytes(n, n_bins, S, int(model))
-    if nbytes < 0:
-        _hip.check(int(nbytes), "lr_loo_workspace_bytes")
-    plan = loo_plan(n, n_bins, S, model)
-    pw = alloc_output((n, 4), torch.float64, ts.device)
-    tot = alloc_output(10, torch.float64, ts.device)
-    ws = alloc_workspace(nbytes, ts.device, cached=True)
-    rc = _hip.launch(lib.lr_loo_pointwise, ts.device, _hip.ptr(ts), _hip.ptr(te), n, float(t0), n_bins, _hip.ptr(lam), _hip.ptr(mu),
-                     S, int(model), _hip.ptr(br), float(end_time), _hip.ptr(pw), _hip.ptr(tot), _hip.ptr(ws), ws.numel())
-    _hip.check(rc, "lr_loo_pointwise")
+    pw, tot, plan, ws, n, S = _draws_pointwise(lib.lr_loo_workspace_bytes, loo_plan, lib.lr_loo_pointwise, 4, 10, ts, te, t0,
+                                               lam_bins, mu_bins, model, br_length, end_time)
     if return_terms:
         if plan[3] != 1:
             raise ValueError("return_terms: the call took %d batches; the workspace holds the last one only" % plan[3])
-        return pw, tot, plan, ws[:n * S * 8].view(torch.float64).reshape(n, S).clone()
+        return pw, tot, plan, ws[:n * S * 8].view(pw.dtype).reshape(n, S).clone()
     return pw, tot, plan
 
 

@@ -132,6 +132,14 @@ def draw_rates(flat_rows, idx, n_bins):
     return out[0], out[1]
 
 
+def chunked_rates(rates_of, par):
+    """(lam_bins, mu_bins) of the parameter vectors par [R, W] (device): rates_of on at most 65535 of them a launch (what
+    lr_dd_rates and lr_trend_rates take), its first two results"""
+    import torch
+    parts = [rates_of(par[a:a + 65535])[:2] for a in range(0, par.shape[0], 65535)]
+    return torch.cat([q[0] for q in parts]), torch.cat([q[1] for q in parts])
+
+
 def _check(R, sp, ex, spb, seed, free_sim, step_sim, start_bin, capacity, start_time):
     """Steps 2 - 4 around two simulator calls -> (div_obs, b0, cap, free, step, table, fit).  free_sim(b0, n_start, seed, cap)
     runs R replicates over bins b0 .. n_bins - 1; step_sim(b0, n1, seed, cap) runs the (n_bins - b0) * R one-bin replicates
@@ -278,9 +286,7 @@ def posterior_predictive_dd(rows, sp_events, ex_events, DT, time_range, m_birth,
     par = flat[torch.as_tensor(idx, device=flat.device)][:, 4:12].contiguous()
     dev = par.device
     spb, seed, mb, md = int(steps_per_bin), int(seed), int(m_birth), int(m_death)
-    # (lr_dd_rates takes at most 65535 parameter vectors a launch)
-    parts = [ops.dd_rates(par[a:a + 65535], DT, mb, md)[:2] for a in range(0, R, 65535)]
-    lam, mu = torch.cat([q[0] for q in parts]), torch.cat([q[1] for q in parts])
+    lam, mu = chunked_rates(lambda q: ops.dd_rates(q, DT, mb, md), par)
     xd = torch.as_tensor(x, device=dev)
 
     def free_sim(b0, n_start, seed_, cap):
@@ -362,19 +368,14 @@ def write_run_ppc_dd(eng, n_local, total_chains, world, rank, burnin, n_draws, s
 
 
 def write_run_ppc_trend(eng, n_local, total_chains, world, rank, burnin, n_draws, steps_per_bin, seed, stem, start_bin=None):
-    """trend_rate.py's --ppc: the rates of the drawn rows by ops.trend_rates (fixed per bin: the covariate is data), then
-    posterior_predictive_rates, on rank 0 -> the two files and one line on stdout."""
-    from . import ops
-    import torch
+    """trend_rate.py's --ppc: the rates of the drawn rows by the engine's draw_rates (fixed per bin: the covariate is data),
+    then posterior_predictive_rates, on rank 0 -> the two files and one line on stdout."""
     rows = _gathered_rows(eng, n_local, total_chains, world, burnin)
     if rank != 0:
         return None
     flat = rows.reshape(-1, LR_TRACE_W)
     idx = draw_indices(flat.shape[0], n_draws)
-    par = flat[torch.as_tensor(idx, device=flat.device)][:, 4:10].contiguous()
-    # (lr_trend_rates takes at most 65535 parameter vectors a launch)
-    parts = [ops.trend_rates(par[a:a + 65535], eng.trend, eng.const_birth, eng.const_death) for a in range(0, len(idx), 65535)]
-    lam, mu = torch.cat([q[0] for q in parts]), torch.cat([q[1] for q in parts])
+    lam, mu = eng.draw_rates(flat, idx)
     res = posterior_predictive_rates(lam, mu, eng.n_spec, eng.n_exti, steps_per_bin, seed, start_bin=start_bin,
                                      start_time=float(eng.origin), draw_rows=idx)
     return _write_and_say(stem, res)

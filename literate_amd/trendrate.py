@@ -78,6 +78,14 @@ class TrendRateEngine(ChainEngine):
                 O[:, 12 + 2 * n:] = logs.adequacy_rows(emp[0], emp[1], b, d)
         return out.reshape(lead + (out.shape[1],))
 
+    def draw_rates(self, flat_rows, idx):
+        """per-bin rates (lam_bins, mu_bins) [R, n_bins] of rows idx of the flat trace rows (device): ops.trend_rates of
+        their columns 4:10"""
+        from . import ppc
+        import torch
+        par = flat_rows[torch.as_tensor(idx, device=flat_rows.device)][:, 4:10].contiguous()
+        return ppc.chunked_rates(lambda q: ops.trend_rates(q, self.trend, self.const_birth, self.const_death), par)
+
     def ess_rows(self, rows):
         """The trace rows as they are: posterior, likelihood, prior and the six parameters l_min .. gamma (columns 1-9)."""
         return rows, list(range(1, 10)), ["it", "posterior", "likelihood", "prior"] + LOG_HEAD[6:12]

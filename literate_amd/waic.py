@@ -42,22 +42,29 @@ fingerprint [6] (FINGERPRINT); plan = (lineages per tile, draws per LDS chunk, d
 rows the draws came from (None when rates were given directly)."""
 
 
+def _arg_error(flag, few_draws, burnin, n_draws, model, pyrate_output, rm_first_bin):
+    """arg_error's rules for the CLI flag `flag` ("--waic", "--loo"); few_draws: what to say of fewer than 2 draws"""
+    if not (0.0 <= burnin < 1.0):
+        return "%s takes a burn-in fraction in [0, 1)" % flag
+    if n_draws < 2:
+        return few_draws
+    if model == 1:
+        return ("%s sums per-lineage terms; under -model_BDI 1 (immigration-death) the likelihood carries a per-bin "
+                "constant that belongs to no lineage: not supported together" % flag)
+    if rm_first_bin:
+        return ("%s scores every lineage of the data; under -rm_first_bin 1 the lineages of the removed bin would be "
+                "scored outside the window the model was fitted on: not supported together" % flag)
+    if pyrate_output:
+        return ("%s reads the AD / TBP times of the trace; -pyrate_output flips them in the logs: not supported together"
+                % flag)
+    return None
+
+
 def arg_error(burnin, n_draws, model=2, pyrate_output=False, rm_first_bin=False):
     """Why a CLI's --waic BURNIN cannot run (None when it can).  LiteRateForward.py passes its -model_BDI and
     -pyrate_output, DDRate.py / trend_rate.py their -rm_first_bin."""
-    if not (0.0 <= burnin < 1.0):
-        return "--waic takes a burn-in fraction in [0, 1)"
-    if n_draws < 2:
-        return "--waic_draws must be at least 2 (a variance over the draws)"
-    if model == 1:
-        return ("--waic sums per-lineage terms; under -model_BDI 1 (immigration-death) the likelihood carries a per-bin "
-                "constant that belongs to no lineage: not supported together")
-    if rm_first_bin:
-        return ("--waic scores every lineage of the data; under -rm_first_bin 1 the lineages of the removed bin would be "
-                "scored outside the window the model was fitted on: not supported together")
-    if pyrate_output:
-        return "--waic reads the AD / TBP times of the trace; -pyrate_output flips them in the logs: not supported together"
-    return None
+    return _arg_error("--waic", "--waic_draws must be at least 2 (a variance over the draws)", burnin, n_draws, model,
+                      pyrate_output, rm_first_bin)
 
 
 def fingerprint(ts, te, t0, n_bins, model):
@@ -78,93 +85,57 @@ def waic_from_rates(ts, te, t0, lam_bins, mu_bins, model=2, br_length=None, end_
                       draw_rows)
 
 
-def _drawn(rows, n_draws):
+def _write_row(path, head, ints, vals):
+    """a tsv of one row under `head`: numbers as str(float), the columns named in `ints` as integers"""
+    with open(path, "w") as f:
+        f.write("\t".join(head) + "\n")
+        f.write("\t".join("%d" % v if k in ints else str(float(v)) for k, v in zip(head, vals)) + "\n")
+
+
+def write_files(stem, res):
+    """<stem>_WAIC.tsv (TSV_HEAD, one row; numbers as str(float), counts as integers) and <stem>_WAIC_pointwise.npz (elpd [n]
+    in the order of the scored lineages, NaN where flagged; fingerprint [6])."""
+    _write_row(stem + "_WAIC.tsv", TSV_HEAD, TSV_INTS,
+               [res.draws, res.lineages, res.lineages_used, res.lineages_flagged, res.lppd, res.p_waic, res.elpd_waic, res.se_elpd,
+                res.waic, res.se_waic, res.n_var_gt_04, res.max_var])
+    np.savez(stem + "_WAIC_pointwise.npz", elpd=np.asarray(res.elpd, dtype=np.float64), fingerprint=res.fingerprint)
+
+
+def _say(stem, res):
+    return ("WAIC: %s_WAIC.tsv, %s_WAIC_pointwise.npz (%d draws, %d lineages, %d flagged; elpd_waic %.6f, se %.6f, p_waic %.6f; "
+            "%d lineages with var > 0.4)" % (stem, stem, res.draws, res.lineages, res.lineages_flagged, res.elpd_waic, res.se_elpd,
+                                            res.p_waic, res.n_var_gt_04))
+
+
+def _run(from_rates, write, say, eng, n_local, total_chains, world, rank, burnin, n_draws, stem, cap=None):
+    """What --waic and --loo do after a run: the rows it sampled, int(burnin * S) dropped per chain, gathered to rank 0; there
+    n_draws of them chosen as --ppc chooses them, their per-bin rates by the engine's own draw_rates, scored by from_rates
+    against the engine's lineages, window, model id and br_length -> write's two files and say's line on stdout.
+    cap: (most n_draws the criterion takes, what to say of more)."""
     from . import ppc
     from ._hip import LR_TRACE_W
-    import torch
+    rows = ppc._gathered_rows(eng, n_local, total_chains, world, burnin)     # (every rank calls: a collective)
+    if rank != 0:
+        return None
+    if cap is not None and n_draws > cap[0]:
+        raise ValueError(cap[1])
     if rows.dim() != 3 or rows.shape[2] != LR_TRACE_W:
         raise ValueError("rows must be [samples, chains, LR_TRACE_W]")
     flat = rows.reshape(-1, LR_TRACE_W)
     idx = ppc.draw_indices(flat.shape[0], n_draws)
     if len(idx) < 2:
         raise ValueError("WAIC needs at least 2 draws (%d post-burn-in rows)" % flat.shape[0])
-    return flat, idx, torch
-
-
-def _score(eng, lam, mu, idx):
-    return waic_from_rates(eng.ts, eng.te, eng.t0, lam, mu, model=eng.model,
-                           br_length=eng.br_length if eng.model == 0 else None, end_time=eng.end_time, draw_rows=idx)
-
-
-def waic_of_rows(eng, rows, n_draws):
-    """LiteRateForward's engine: the drawn rows' per-bin rates by ppc.draw_rates, scored on the engine's lineages"""
-    from . import ppc
-    flat, idx, _ = _drawn(rows, n_draws)
-    lam, mu = ppc.draw_rates(flat, idx, eng.n_bins)
-    return _score(eng, lam, mu, idx)
-
-
-def waic_of_rows_dd(eng, rows, n_draws):
-    """DDRate's engine: ops.dd_rates of the drawn rows' columns 4:12 at the observed DT"""
-    from . import ops
-    flat, idx, torch = _drawn(rows, n_draws)
-    par = flat[torch.as_tensor(idx, device=flat.device)][:, 4:12].contiguous()
-    # (lr_dd_rates takes at most 65535 parameter vectors a launch)
-    parts = [ops.dd_rates(par[a:a + 65535], eng.DT, eng.m_birth, eng.m_death)[:2] for a in range(0, len(idx), 65535)]
-    return _score(eng, torch.cat([q[0] for q in parts]), torch.cat([q[1] for q in parts]), idx)
-
-
-def waic_of_rows_trend(eng, rows, n_draws):
-    """trend_rate's engine: ops.trend_rates of the drawn rows' columns 4:10"""
-    from . import ops
-    flat, idx, torch = _drawn(rows, n_draws)
-    par = flat[torch.as_tensor(idx, device=flat.device)][:, 4:10].contiguous()
-    # (lr_trend_rates takes at most 65535 parameter vectors a launch)
-    parts = [ops.trend_rates(par[a:a + 65535], eng.trend, eng.const_birth, eng.const_death) for a in range(0, len(idx), 65535)]
-    return _score(eng, torch.cat([q[0] for q in parts]), torch.cat([q[1] for q in parts]), idx)
-
-
-def write_files(stem, res):
-    """<stem>_WAIC.tsv (TSV_HEAD, one row; numbers as str(float), counts as integers) and <stem>_WAIC_pointwise.npz (elpd [n]
-    in the order of the scored lineages, NaN where flagged; fingerprint [6])."""
-    vals = [res.draws, res.lineages, res.lineages_used, res.lineages_flagged, res.lppd, res.p_waic, res.elpd_waic, res.se_elpd,
-            res.waic, res.se_waic, res.n_var_gt_04, res.max_var]
-    with open(stem + "_WAIC.tsv", "w") as f:
-        f.write("\t".join(TSV_HEAD) + "\n")
-        f.write("\t".join("%d" % v if k in TSV_INTS else str(float(v)) for k, v in zip(TSV_HEAD, vals)) + "\n")
-    np.savez(stem + "_WAIC_pointwise.npz", elpd=np.asarray(res.elpd, dtype=np.float64), fingerprint=res.fingerprint)
-
-
-def _write_and_say(stem, res):
-    write_files(stem, res)
-    print("WAIC: %s_WAIC.tsv, %s_WAIC_pointwise.npz (%d draws, %d lineages, %d flagged; elpd_waic %.6f, se %.6f, p_waic %.6f; "
-          "%d lineages with var > 0.4)" % (stem, stem, res.draws, res.lineages, res.lineages_flagged, res.elpd_waic, res.se_elpd,
-                                          res.p_waic, res.n_var_gt_04))
+    lam, mu = eng.draw_rates(flat, idx)
+    res = from_rates(eng.ts, eng.te, eng.t0, lam, mu, model=eng.model, br_length=eng.br_length if eng.model == 0 else None,
+                     end_time=eng.end_time, draw_rows=idx)
+    write(stem, res)
+    print(say(stem, res))
     return res
 
 
-def _run(of_rows, eng, n_local, total_chains, world, rank, burnin, n_draws, stem):
-    from . import ppc
-    rows = ppc._gathered_rows(eng, n_local, total_chains, world, burnin)     # (every rank calls: a collective)
-    if rank != 0:
-        return None
-    return _write_and_say(stem, of_rows(eng, rows, n_draws))
-
-
-def write_run_waic(eng, n_local, total_chains, world, rank, burnin, n_draws, stem):
-    """LiteRateForward.py's --waic: the rows the run sampled, int(burnin * S) dropped per chain, gathered to rank 0 and
-    scored against the engine's own lineages, window, model id and br_length -> the two files and one line on stdout."""
-    return _run(waic_of_rows, eng, n_local, total_chains, world, rank, burnin, n_draws, stem)
-
-
-def write_run_waic_dd(eng, n_local, total_chains, world, rank, burnin, n_draws, stem):
-    """DDRate.py's --waic (rates: ops.dd_rates at the observed DT, the log's l_i / m_i columns)."""
-    return _run(waic_of_rows_dd, eng, n_local, total_chains, world, rank, burnin, n_draws, stem)
-
-
-def write_run_waic_trend(eng, n_local, total_chains, world, rank, burnin, n_draws, stem):
-    """trend_rate.py's --waic (rates: ops.trend_rates of the drawn parameters)."""
-    return _run(waic_of_rows_trend, eng, n_local, total_chains, world, rank, burnin, n_draws, stem)
+def write_run(eng, n_local, total_chains, world, rank, burnin, n_draws, stem):
+    """The three CLIs' --waic (_run with waic_from_rates): <stem>_WAIC.tsv, <stem>_WAIC_pointwise.npz, one line on stdout."""
+    return _run(waic_from_rates, write_files, _say, eng, n_local, total_chains, world, rank, burnin, n_draws, stem)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -205,53 +176,68 @@ def compare_arrays(names, elpds, p_waics=None):
     return rows
 
 
-def _p_waic_beside(path):
-    """p_waic of the <stem>_WAIC.tsv that write_files left beside <stem>_WAIC_pointwise.npz (nan when it is not there)"""
+def _beside(path, name):
+    """column `name` of the one-row <stem>_X.tsv that write_files left beside <stem>_X_pointwise.npz (nan when it is not there)"""
     import os
     tsv = path[:-len("_pointwise.npz")] + ".tsv" if path.endswith("_pointwise.npz") else None
     if not tsv or not os.path.exists(tsv):
         return float("nan")
     with open(tsv) as f:
         head, row = f.readline().rstrip("\n").split("\t"), f.readline().rstrip("\n").split("\t")
-    return float(row[head.index("p_waic")]) if "p_waic" in head and len(row) == len(head) else float("nan")
+    return float(row[head.index(name)]) if name in head and len(row) == len(head) else float("nan")
 
 
-def compare(paths):
-    """Two or more <stem>_WAIC_pointwise.npz -> rows sorted by elpd (compare_arrays); ValueError unless every file's
-    fingerprint equals the first one's (the runs were then not scored on the same lineages, window and model id)."""
+def _comparable(paths, read):
+    """read(path, npz) -> a tuple that begins (elpd, fingerprint, ...) for each of two or more pointwise files; ValueError
+    unless every file's fingerprint (and number of lineages) equals the first one's"""
     paths = list(paths)
     if len(paths) < 2:
         raise ValueError("compare takes two or more pointwise files")
     loaded = []
     for p in paths:
         with np.load(p) as z:
-            loaded.append((np.asarray(z["elpd"], dtype=np.float64), np.asarray(z["fingerprint"], dtype=np.float64)))
-    for p, (e, fp) in zip(paths[1:], loaded[1:]):
-        bad = fingerprint_mismatch(loaded[0][1], fp)
-        if bad is None and len(e) != len(loaded[0][0]):
+            loaded.append(read(p, z))
+    for p, rec in zip(paths[1:], loaded[1:]):
+        bad = fingerprint_mismatch(loaded[0][1], rec[1])
+        if bad is None and len(rec[0]) != len(loaded[0][0]):
             bad = "n"
         if bad:
             raise ValueError("fingerprint mismatch (%s): %s and %s were not scored on the same lineages, window and model id; "
                              "their WAIC values are not comparable" % (bad, paths[0], p))
-    return compare_arrays(paths, [e for e, _ in loaded], [_p_waic_beside(p) for p in paths])
+    return paths, loaded
 
 
-def format_table(rows):
-    lines = ["\t".join(COMPARE_HEAD)]
+def compare(paths):
+    """Two or more <stem>_WAIC_pointwise.npz -> rows sorted by elpd (compare_arrays); ValueError unless every file's
+    fingerprint equals the first one's (the runs were then not scored on the same lineages, window and model id)."""
+    paths, loaded = _comparable(paths, lambda p, z: (np.asarray(z["elpd"], dtype=np.float64),
+                                                     np.asarray(z["fingerprint"], dtype=np.float64)))
+    return compare_arrays(paths, [e for e, _ in loaded], [_beside(p, "p_waic") for p in paths])
+
+
+def _format_rows(head, rows):
+    """rows (dicts) under `head`: the model's name, four numbers as str(float), the remaining columns as integers"""
+    lines = ["\t".join(head)]
     for r in rows:
-        lines.append("\t".join([str(r["model"])] + [str(float(r[k])) for k in COMPARE_HEAD[1:5]] + ["%d" % r["lineages_used"]]))
+        lines.append("\t".join([str(r["model"])] + [str(float(r[k])) for k in head[1:5]] + ["%d" % r[k] for k in head[5:]]))
     return "\n".join(lines) + "\n"
 
 
-def main(argv=None):
+def format_table(rows):
+    return _format_rows(COMPARE_HEAD, rows)
+
+
+def _main(argv, module, name, tag, compare_, format_):
+    """python -m literate_amd.<module>: the table of compare_ on stdout (and in -o).  name and tag: "WAIC" and "WAIC",
+    "PSIS-LOO" and "LOO"."""
     import argparse
-    p = argparse.ArgumentParser(prog="python -m literate_amd.waic",
-                                description="rank runs by WAIC from their <stem>_WAIC_pointwise.npz files")
-    p.add_argument("files", nargs="+", help="two or more <stem>_WAIC_pointwise.npz written by --waic")
+    p = argparse.ArgumentParser(prog="python -m literate_amd.%s" % module,
+                                description="rank runs by %s from their <stem>_%s_pointwise.npz files" % (name, tag))
+    p.add_argument("files", nargs="+", help="two or more <stem>_%s_pointwise.npz written by --%s" % (tag, module))
     p.add_argument("-o", default="", help="also write the table to this file")
     args = p.parse_args(argv)
     try:
-        text = format_table(compare(args.files))
+        text = format_(compare_(args.files))
     except ValueError as ex:
         raise SystemExit(str(ex))
     print(text, end="")
@@ -259,6 +245,10 @@ def main(argv=None):
         with open(args.o, "w") as f:
             f.write(text)
     return 0
+
+
+def main(argv=None):
+    return _main(argv, "waic", "WAIC", "WAIC", compare, format_table)
 
 
 if __name__ == "__main__":

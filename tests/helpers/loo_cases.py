@@ -252,12 +252,20 @@ def prepare_rates(cfg, model):
 
 
 def case_rates(model):
-    """ops.loo_pointwise against the restatement fed the same rates"""
-    import torch
+    """ops.loo_pointwise against the restatement fed the same rates; then the walk's middle LDS regime (waic_cases.MIDDLE:
+    one batch of all 257 lineages), with a bound of its own"""
     from literate_amd import ops
     model = int(model)
+    run_rate_configs(rate_configs(model), model)
+    mid = waic_cases.MIDDLE
+    assert ops.loo_plan(mid["n"], mid["n_bins"], mid["S"], model)[2:] == (257, 1)
+    run_rate_configs([mid], model)
+
+
+def run_rate_configs(configs, model):
+    from literate_amd import ops
     prepared, worst = [], np.zeros(4)
-    for cfg in rate_configs(model):
+    for cfg in configs:
         ts, te, lam, mu, br, end, ld, f64, u, exempt = prepare_rates(cfg, model)
         share = float(exempt.mean())
         say("model %d %s: %d of %d lineages with an ambiguous tail" % (model, {k: cfg[k] for k in ("n", "n_bins", "S", "kind")}, exempt.sum(), cfg["n"]))
@@ -280,7 +288,6 @@ def case_rates(model):
         assert (c <= allowed).all(), (cfg, c, allowed)
         check_totals(tot, pw, ld, allowed, loo_ref.value_units(ld, u))
     say("device, worst counts (elpd_loo, pareto_k, lppd, n_eff): %s" % dev_worst)
-    del torch
 
 
 def case_exact():

@@ -156,6 +156,12 @@ def run_configs(configs, model):
     return worst, dev_worst
 
 
+# Between the groups' bin counts (<= 263: several draws' tables per LDS buffer) and the largest accepted (one table, one
+# buffer) lies the walk's middle regime: a draw's table above 16 KiB, two of them in LDS (38,464 B under models 0 and 2,
+# 76,928 B under model 3), so the plan's chunk is 1 and the next table lands in the other buffer.
+MIDDLE = dict(n=257, n_bins=1200, S=25, kind="continuous", shuffled=True, offset=False, seed=3201)
+
+
 def case_against(model, group):
     """the device against the restatement at the table-size edges of one group of bin counts, every draw count around the
     LDS chunk, every lineage count, kind of times, order and alignment"""
@@ -175,6 +181,9 @@ def case_against(model, group):
                 configs.append(dict(n=n, n_bins=nb, S=S, kind=KINDS[k % 3], shuffled=bool(k & 1), offset=bool(k & 2), seed=1000 + k))
                 k += 1
     run_configs(configs, model)
+    if group == "d":                                              # (with a bound of its own: the others' stays what it was)
+        assert ops.waic_plan(MIDDLE["n"], MIDDLE["n_bins"], MIDDLE["S"], model)[1] == 1
+        run_configs([MIDDLE], model)
 
 
 def case_exact():

@@ -167,13 +167,11 @@ def main(argv=None):
                             "%s_%s" % (stem, args.trend_index),
                             start_bin=args.ppc_start_bin if args.ppc_start_bin >= 0 else None)
     if args.waic != -1.0 and n_samples:
-        from literate_amd.waic import write_run_waic_trend
-        write_run_waic_trend(eng, n_local, args.chains, world, rank, args.waic, args.waic_draws,
-                             "%s_%s" % (stem, args.trend_index))
+        from literate_amd import waic
+        waic.write_run(eng, n_local, args.chains, world, rank, args.waic, args.waic_draws, "%s_%s" % (stem, args.trend_index))
     if args.loo != -1.0 and n_samples:
-        from literate_amd.loo import write_run_loo_trend
-        write_run_loo_trend(eng, n_local, args.chains, world, rank, args.loo, args.loo_draws,
-                            "%s_%s" % (stem, args.trend_index))
+        from literate_amd import loo
+        loo.write_run(eng, n_local, args.chains, world, rank, args.loo, args.loo_draws, "%s_%s" % (stem, args.trend_index))
     eng.close()
     if world > 1:
         dist.barrier()
