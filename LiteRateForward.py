@@ -74,6 +74,12 @@ def build_parser():
     p.add_argument('--ppc_scale', type=int, default=100, help='simulation steps per time unit (the reference Simulator.scale)')
     p.add_argument('--ppc_start_bin', type=int, default=-1, help='bin at whose left edge the free-running simulations start '
                    '(default: the first bin after bin 0 that starts with an observed lineage)')
+    p.add_argument('--ppc_age', type=float, default=-1.0, help='after the run, write <stem>_PPC_age.tsv and <stem>_PPC_age_fit.tsv next '
+                   'to the logs: the lifespan check - every lineage, born when the data say, is given a death time under '
+                   '--ppc_age_draws posterior draws of the death rates (this burn-in fraction dropped per chain), and the '
+                   'predicted deaths and hazard by AGE are set beside the observed ones: does the chance of dying depend '
+                   'on age, which the model assumes it does not; simulated on the GPU; not with -model_BDI 3 or -pyrate_output')
+    p.add_argument('--ppc_age_draws', type=int, default=1000, help='posterior draws the lifespan check simulates under')
     p.add_argument('--waic', type=float, default=-1.0, help='after the run, write <stem>_WAIC.tsv and <stem>_WAIC_pointwise.npz next to the logs: WAIC (elpd, '
                    'p_waic and their standard errors) from --waic_draws posterior draws of the rates (this burn-in '
                    'fraction dropped per chain), the log-likelihood term of each lineage reduced over the draws on the GPU; '
@@ -144,6 +150,11 @@ def main(argv=None):
             raise SystemExit(err)
         if args.ppc_draws < 1 or args.ppc_scale < 1:
             raise SystemExit("--ppc_draws and --ppc_scale must be at least 1")
+    if args.ppc_age != -1.0:
+        from literate_amd.ppc_age import arg_error as age_arg_error
+        err = age_arg_error(args.ppc_age, args.ppc_age_draws, model=args.model_BDI, pyrate_output=args.pyrate_output)
+        if err:
+            raise SystemExit(err)
     if args.waic != -1.0:
         from literate_amd.waic import arg_error as waic_arg_error
         err = waic_arg_error(args.waic, args.waic_draws, model=args.model_BDI, pyrate_output=args.pyrate_output)
@@ -283,6 +294,10 @@ def main(argv=None):
         stem = logs.log_paths(args.d, args.model_BDI, args.out)[1]["div"][:-len("_div.log")]
         ppc.write_run_ppc(eng, sp, ex, n_local, args.chains, world, rank, args.ppc, args.ppc_draws, args.ppc_scale, rseed,
                           stem, start_bin=args.ppc_start_bin if args.ppc_start_bin >= 0 else None)
+    if args.ppc_age != -1.0 and n_samples:
+        from literate_amd import ppc_age
+        stem = logs.log_paths(args.d, args.model_BDI, args.out)[1]["div"][:-len("_div.log")]
+        ppc_age.write_run(eng, n_local, args.chains, world, rank, args.ppc_age, args.ppc_age_draws, rseed, stem)
     if args.waic != -1.0 and n_samples:
         from literate_amd import waic
         stem = logs.log_paths(args.d, args.model_BDI, args.out)[1]["div"][:-len("_div.log")]

@@ -1,4 +1,4 @@
-"""ctypes binding of libliterate_hip.so (include/literate_hip.h).  Fails loudly: no fallback."""
+"""ctypes binding of libliterate_hip.so (include/literate_hip.h, include/literate_hip_age.h).  Fails loudly: no fallback."""
 import ctypes as C
 import os
 
@@ -46,7 +46,7 @@ class McmcLayout(C.Structure):
                 ("spec_chains_per_team", c_i32), ("streaming", c_i32), ("packed_scan", c_i32), ("reserved3", c_i32)]
 
 
-# name -> (restype, argtypes); exactly the symbols include/literate_hip.h declares (+ the RNG debug hook)
+# name -> (restype, argtypes); exactly the symbols include/literate_hip.h and literate_hip_age.h declare (+ the RNG debug hook)
 SIGNATURES = {
     "lr_version": (c_i32, []),
     "lr_bin_events_workspace_bytes": (c_i64, [c_i64, c_i32]),
@@ -87,6 +87,9 @@ SIGNATURES = {
     "lr_rtt_summary_workspace_bytes": (c_i64, [c_i32, c_i32, c_f64, c_f64, c_f64, c_i32]),
     "lr_rtt_summary": (c_i32, [c_vp, c_i32, c_i32, c_f64, c_f64, c_f64, c_i32, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
     "lr_shift_prior": (c_i32, [c_f64, c_f64, c_i64, c_i64, C.c_uint64, c_f64, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "lr_ppc_age_workspace_bytes": (c_i64, [c_i64, c_i32, c_i32]),
+    "lr_ppc_age_plan": (c_i32, [c_i64, c_i32, c_i32, C.POINTER(c_i32)]),
+    "lr_ppc_age": (c_i32, [c_vp, c_vp, c_i64, c_f64, c_i32, c_vp, c_i32, C.c_uint64, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
     "lr_ess_summary_workspace_bytes": (c_i64, [c_i32, c_i32, c_i32, c_vp, c_i32, c_f64, c_i32]),
     "lr_ess_summary": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_i32, c_f64, c_i32, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
     "lr_col_summary_workspace_bytes": (c_i64, [c_i32, c_i32, c_i32, c_vp, c_i32, c_f64, c_i32, c_i32]),

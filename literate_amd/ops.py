@@ -702,6 +702,55 @@ def shift_prior(start_age, end_age, n_reps=1 << 20, seed=0, poi_lambda=None, rep
     return res
 
 
+PPC_AGE_TOTALS = ("lineages_used", "lineages_unused", "draws_used", "draws_flagged")
+PPC_AGE_PLAN = ("lineages_per_tile", "draws_per_slice", "draw_slices", "tiles")
+
+
+def ppc_age_plan(n, n_bins, n_draws):
+    """lr_ppc_age_plan: (lineages per tile, draws per slice, slices, tiles) - a function of the sizes alone (host;
+    LR_PPC_AGE_SLICES in the environment is read per call)."""
+    import ctypes as C
+    import torch  # noqa: F401  (before the library, as everywhere here: both must bind the HIP runtime torch ships)
+    lib = _hip.load()
+    out = (C.c_int32 * 4)()
+    _hip.check(lib.lr_ppc_age_plan(int(n), int(n_bins), int(n_draws), out), "lr_ppc_age_plan")
+    return tuple(int(v) for v in out)
+
+
+def ppc_age(ts, te, t0, mu_bins, seed, out=None):
+    """Posterior predictive deaths by age (lr_ppc_age, include/literate_hip_age.h): every lineage, born at its ts, dies
+    under every one of the S draws of per-bin death rates mu_bins [S, n_bins] -> (obs [2, A] observed dead / censored per
+    age class, rep [S, 2, A] simulated dead / survivors per draw and class - all -1 for a flagged draw -, totals [4]
+    (PPC_AGE_TOTALS), plan (PPC_AGE_PLAN, host tuple)); int64 tensors on the device, A = n_bins.  The Philox counter of a
+    pair is (position of the lineage in ts / te, draw), the key `seed`.  out: the (obs, rep, totals) of an earlier call of
+    the same sizes to write into (they may hold anything)."""
+    torch = _torch()
+    lib = _hip.load()
+    ts = _dev(ts, torch.float64)
+    te = _dev(te, torch.float64, ts.device)
+    mu = _dev(mu_bins, torch.float64, ts.device)
+    if mu.dim() != 2 or ts.dim() != 1 or te.numel() != ts.numel():
+        raise ValueError("shape mismatch: ts, te [n]; mu_bins [draws, n_bins]")
+    S, A = (int(v) for v in mu.shape)
+    n, dev = ts.numel(), ts.device
+    nbytes = lib.lr_ppc_age_workspace_bytes(n, A, S)
+    if nbytes < 0:
+        _hip.check(int(nbytes), "lr_ppc_age_workspace_bytes")
+    plan = ppc_age_plan(n, A, S)
+    if out is None:
+        obs, rep, tot = (alloc_output(shape, torch.int64, dev) for shape in ((2, A), (S, 2, A), 4))
+    else:
+        obs, rep, tot = out[:3]
+        if any(t.dtype != torch.int64 or tuple(t.shape) != shape or not t.is_contiguous() or t.device != dev
+               for t, shape in zip((obs, rep, tot), ((2, A), (S, 2, A), (4,)))):
+            raise ValueError("out must be the (obs, rep, totals) of a call of the same sizes")
+    ws = alloc_workspace(nbytes, dev, cached=True)
+    rc = _hip.launch(lib.lr_ppc_age, dev, _hip.ptr(ts), _hip.ptr(te), n, float(t0), A, _hip.ptr(mu), S,
+                     int(seed) & 0xFFFFFFFFFFFFFFFF, _hip.ptr(obs), _hip.ptr(rep), _hip.ptr(tot), _hip.ptr(ws), ws.numel())
+    _hip.check(rc, "lr_ppc_age")
+    return obs, rep, tot, plan
+
+
 EssSummary = namedtuple("EssSummary", "mean ess act se_mean stop_lag pooled_mean pooled_ess rhat n")
 EssSummary.__doc__ = """lr_ess_summary's results.  mean, ess, act (in samples), se_mean float64 and stop_lag int32: [C, K] per chain and
 column; pooled_mean, pooled_ess, rhat: [K]; n: rows kept per chain.  ESS and ACT are NaN, SE 0 and the stop lag 0 where a

@@ -46,6 +46,12 @@ def build_parser():
     p.add_argument('--ppc_scale', type=int, default=100, help='simulation steps per time unit (the reference Simulator.scale)')
     p.add_argument('--ppc_start_bin', type=int, default=-1, help='bin at whose left edge the free-running simulations start '
                    '(default: the first bin after bin 0 that starts with an observed lineage)')
+    p.add_argument('--ppc_age', type=float, default=-1.0, help='after the run, write <stem>_PPC_age.tsv and <stem>_PPC_age_fit.tsv beside '
+                   'the logs: the lifespan check - every lineage, born when the data say, is given a death time under '
+                   '--ppc_age_draws posterior draws of the per-bin death rates (this burn-in fraction dropped per chain), and '
+                   'the predicted deaths and hazard by AGE are set beside the observed ones: does the chance of dying depend '
+                   'on age, which the model assumes it does not; simulated on the GPU; not with -rm_first_bin 1 (extension)')
+    p.add_argument('--ppc_age_draws', type=int, default=1000, help='posterior draws the lifespan check simulates under')
     p.add_argument('--waic', type=float, default=-1.0, help='after the run, write <stem>_WAIC.tsv and <stem>_WAIC_pointwise.npz beside the logs: WAIC (elpd, '
                    'p_waic and their standard errors) from --waic_draws posterior draws of the parameters, at the '
                    'per-bin rates the trend gives them (this burn-in fraction dropped per chain), the per-lineage '
@@ -79,6 +85,11 @@ def main(argv=None):
     if args.ppc != -1.0:
         from literate_amd.ppc import dd_arg_error
         err = dd_arg_error(args.ppc, args.rm_first_bin, args.ppc_draws, args.ppc_scale)
+        if err:
+            raise SystemExit(err)
+    if args.ppc_age != -1.0:
+        from literate_amd.ppc_age import arg_error as age_arg_error
+        err = age_arg_error(args.ppc_age, args.ppc_age_draws, rm_first_bin=args.rm_first_bin)
         if err:
             raise SystemExit(err)
     if args.waic != -1.0:
@@ -166,6 +177,9 @@ def main(argv=None):
         write_run_ppc_trend(eng, n_local, args.chains, world, rank, args.ppc, args.ppc_draws, args.ppc_scale, seed,
                             "%s_%s" % (stem, args.trend_index),
                             start_bin=args.ppc_start_bin if args.ppc_start_bin >= 0 else None)
+    if args.ppc_age != -1.0 and n_samples:
+        from literate_amd import ppc_age
+        ppc_age.write_run(eng, n_local, args.chains, world, rank, args.ppc_age, args.ppc_age_draws, seed, "%s_%s" % (stem, args.trend_index))
     if args.waic != -1.0 and n_samples:
         from literate_amd import waic
         waic.write_run(eng, n_local, args.chains, world, rank, args.waic, args.waic_draws, "%s_%s" % (stem, args.trend_index))
