@@ -80,6 +80,12 @@ def build_parser():
                    'predicted deaths and hazard by AGE are set beside the observed ones: does the chance of dying depend '
                    'on age, which the model assumes it does not; simulated on the GPU; not with -model_BDI 3 or -pyrate_output')
     p.add_argument('--ppc_age_draws', type=int, default=1000, help='posterior draws the lifespan check simulates under')
+    p.add_argument('--ade', type=float, default=-1.0, help='after the run, write <stem>_ADE.tsv and <stem>_ADE_shape.tsv beside '
+                   'the logs: age-dependent extinction - the Weibull shape of the hazard by lineage age (< 1: a liability of '
+                   'newness, > 1: ageing, 1: what the model assumes), fitted on the GPU conditional on --ade_draws posterior '
+                   'draws of the per-bin death rates (this burn-in fraction dropped per chain), beside the constant-baseline '
+                   'Weibull of the reference ADE scripts; at most 512 time bins; not with -model_BDI 3 or -pyrate_output')
+    p.add_argument('--ade_draws', type=int, default=1000, help='posterior draws the age-dependent extinction fit conditions on')
     p.add_argument('--waic', type=float, default=-1.0, help='after the run, write <stem>_WAIC.tsv and <stem>_WAIC_pointwise.npz next to the logs: WAIC (elpd, '
                    'p_waic and their standard errors) from --waic_draws posterior draws of the rates (this burn-in '
                    'fraction dropped per chain), the log-likelihood term of each lineage reduced over the draws on the GPU; '
@@ -153,6 +159,11 @@ def main(argv=None):
     if args.ppc_age != -1.0:
         from literate_amd.ppc_age import arg_error as age_arg_error
         err = age_arg_error(args.ppc_age, args.ppc_age_draws, model=args.model_BDI, pyrate_output=args.pyrate_output)
+        if err:
+            raise SystemExit(err)
+    if args.ade != -1.0:
+        from literate_amd.ade import arg_error as ade_arg_error
+        err = ade_arg_error(args.ade, args.ade_draws, model=args.model_BDI, pyrate_output=args.pyrate_output)
         if err:
             raise SystemExit(err)
     if args.waic != -1.0:
@@ -298,6 +309,10 @@ def main(argv=None):
         from literate_amd import ppc_age
         stem = logs.log_paths(args.d, args.model_BDI, args.out)[1]["div"][:-len("_div.log")]
         ppc_age.write_run(eng, n_local, args.chains, world, rank, args.ppc_age, args.ppc_age_draws, rseed, stem)
+    if args.ade != -1.0 and n_samples:
+        from literate_amd import ade
+        stem = logs.log_paths(args.d, args.model_BDI, args.out)[1]["div"][:-len("_div.log")]
+        ade.write_run(eng, n_local, args.chains, world, rank, args.ade, args.ade_draws, stem)
     if args.waic != -1.0 and n_samples:
         from literate_amd import waic
         stem = logs.log_paths(args.d, args.model_BDI, args.out)[1]["div"][:-len("_div.log")]

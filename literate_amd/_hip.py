@@ -1,4 +1,4 @@
-"""ctypes binding of libliterate_hip.so (include/literate_hip.h, include/literate_hip_age.h).  Fails loudly: no fallback."""
+"""ctypes binding of libliterate_hip.so (include/literate_hip.h, include/literate_hip_age.h, include/literate_hip_ade.h).  Fails loudly: no fallback."""
 import ctypes as C
 import os
 
@@ -11,6 +11,7 @@ ERRORS = {-1: "LR_ERR_NULL", -2: "LR_ERR_SIZE", -3: "LR_ERR_MODEL", -4: "LR_ERR_
           -6: "LR_ERR_STATE", -7: "LR_ERR_ORDER (lineages must be sorted by birth time for the persistent engines)"}
 
 LR_KMAX, LR_ROW, LR_MAX_BINS = 32, 64, 4094
+LR_ADE_MAX_BINS = 512      # lr_ade_classes, lr_ade_profile (include/literate_hip_ade.h)
 LR_WARN_KCAP = 2
 LR_STATE_ROWS, LR_ISTATE_ROWS = 9, 5
 LR_TRACE_HEAD = 13
@@ -46,7 +47,7 @@ class McmcLayout(C.Structure):
                 ("spec_chains_per_team", c_i32), ("streaming", c_i32), ("packed_scan", c_i32), ("reserved3", c_i32)]
 
 
-# name -> (restype, argtypes); exactly the symbols include/literate_hip.h and literate_hip_age.h declare (+ the RNG debug hook)
+# name -> (restype, argtypes); exactly the symbols include/literate_hip.h, literate_hip_age.h and literate_hip_ade.h declare (+ the RNG debug hook)
 SIGNATURES = {
     "lr_version": (c_i32, []),
     "lr_bin_events_workspace_bytes": (c_i64, [c_i64, c_i32]),
@@ -90,6 +91,9 @@ SIGNATURES = {
     "lr_ppc_age_workspace_bytes": (c_i64, [c_i64, c_i32, c_i32]),
     "lr_ppc_age_plan": (c_i32, [c_i64, c_i32, c_i32, C.POINTER(c_i32)]),
     "lr_ppc_age": (c_i32, [c_vp, c_vp, c_i64, c_f64, c_i32, c_vp, c_i32, C.c_uint64, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "lr_ade_classes": (c_i32, [c_vp, c_vp, c_i64, c_f64, c_i32, c_vp, c_vp, c_vp, c_vp]),
+    "lr_ade_profile_workspace_bytes": (c_i64, [c_i32, c_i32, c_i32]),
+    "lr_ade_profile": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
     "lr_ess_summary_workspace_bytes": (c_i64, [c_i32, c_i32, c_i32, c_vp, c_i32, c_f64, c_i32]),
     "lr_ess_summary": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_i32, c_f64, c_i32, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
     "lr_col_summary_workspace_bytes": (c_i64, [c_i32, c_i32, c_i32, c_vp, c_i32, c_f64, c_i32, c_i32]),

@@ -751,6 +751,71 @@ def ppc_age(ts, te, t0, mu_bins, seed, out=None):
     return obs, rep, tot, plan
 
 
+ADE_TOTALS = ("lineages_used", "lineages_unused")
+
+
+def _ade_out(out, shapes, dtypes, dev, what):
+    """the outputs of an earlier call of the same sizes, checked - or fresh ones"""
+    torch = _torch()
+    if out is None:
+        return tuple(alloc_output(shape, dt, dev) for shape, dt in zip(shapes, dtypes))
+    got = tuple(out[:len(shapes)])
+    if any(t.dtype != dt or tuple(t.shape) != tuple(shape) or not t.is_contiguous() or t.device != dev
+           for t, shape, dt in zip(got, shapes, dtypes)):
+        raise ValueError("out must be the %s of a call of the same sizes" % what)
+    return got
+
+
+def ade_classes(ts, te, t0, n_bins, out=None):
+    """The lineages per (birth bin, age at death) class (lr_ade_classes, include/literate_hip_ade.h) -> (dead [A, A]: dead[jb][a]
+    lineages born in bin jb that died a bins later, cens [A]: alive at the end of the window per birth bin, totals [2]
+    (ADE_TOTALS)); int64 tensors on the device, A = n_bins <= LR_ADE_MAX_BINS.  out: the (dead, cens, totals) of an earlier
+    call of the same sizes to write into (they may hold anything)."""
+    torch = _torch()
+    lib = _hip.load()
+    ts = _dev(ts, torch.float64)
+    te = _dev(te, torch.float64, ts.device)
+    if ts.dim() != 1 or te.numel() != ts.numel():
+        raise ValueError("shape mismatch: ts, te [n]")
+    A, n, dev = int(n_bins), ts.numel(), ts.device
+    if not 1 <= A <= _hip.LR_ADE_MAX_BINS:
+        _hip.check(_hip.LR_ERR_SIZE, "lr_ade_classes")
+    dead, cens, tot = _ade_out(out, ((A, A), (A,), (2,)), (torch.int64,) * 3, dev, "(dead, cens, totals)")
+    rc = _hip.launch(lib.lr_ade_classes, dev, _hip.ptr(ts), _hip.ptr(te), n, float(t0), A, _hip.ptr(dead), _hip.ptr(cens),
+                     _hip.ptr(tot))
+    _hip.check(rc, "lr_ade_classes")
+    return dead, cens, tot
+
+
+def ade_profile(dead, cens, mu_bins, shapes, out=None):
+    """The profile likelihood of the Weibull shape (lr_ade_profile, include/literate_hip_ade.h): for every one of the S draws of
+    per-bin death rates mu_bins [S, A] and every one of the G shapes, the multiplier c that maximises the interval-censored
+    likelihood of the classes (dead [A, A], cens [A]: ade_classes') and the value there -> (ll [S, G], c [S, G] float64,
+    flag [S] int32: 1 for a draw with a rate that is not finite or negative, or zero in a bin that holds a death - its rows
+    are NaN); device tensors.  out: the (ll, c, flag) of an earlier call of the same sizes to write into."""
+    torch = _torch()
+    lib = _hip.load()
+    dead = _dev(dead, torch.int64)
+    dev = dead.device
+    cens = _dev(cens, torch.int64, dev)
+    mu = _dev(mu_bins, torch.float64, dev)
+    sh = _dev(shapes, torch.float64, dev).reshape(-1)
+    if mu.dim() != 2 or dead.dim() != 2 or dead.shape[0] != dead.shape[1] or cens.numel() != dead.shape[0] \
+            or mu.shape[1] != dead.shape[0]:
+        raise ValueError("shape mismatch: dead [A, A]; cens [A]; mu_bins [draws, A]; shapes [G]")
+    S, A = (int(v) for v in mu.shape)
+    G = int(sh.numel())
+    nbytes = lib.lr_ade_profile_workspace_bytes(A, S, G)
+    if nbytes < 0:
+        _hip.check(int(nbytes), "lr_ade_profile_workspace_bytes")
+    ll, c, flag = _ade_out(out, ((S, G), (S, G), (S,)), (torch.float64, torch.float64, torch.int32), dev, "(ll, c, flag)")
+    ws = alloc_workspace(nbytes, dev, cached=True)
+    rc = _hip.launch(lib.lr_ade_profile, dev, _hip.ptr(dead), _hip.ptr(cens), A, _hip.ptr(mu), S, _hip.ptr(sh), G, _hip.ptr(ll),
+                     _hip.ptr(c), _hip.ptr(flag), _hip.ptr(ws), ws.numel())
+    _hip.check(rc, "lr_ade_profile")
+    return ll, c, flag
+
+
 EssSummary = namedtuple("EssSummary", "mean ess act se_mean stop_lag pooled_mean pooled_ess rhat n")
 EssSummary.__doc__ = """lr_ess_summary's results.  mean, ess, act (in samples), se_mean float64 and stop_lag int32: [C, K] per chain and
 column; pooled_mean, pooled_ess, rhat: [K]; n: rows kept per chain.  ESS and ACT are NaN, SE 0 and the stop lag 0 where a
