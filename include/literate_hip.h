@@ -619,6 +619,12 @@ int lr_mcmc_status(lr_engine* e, int32_t* status /* host */, void* stream);
 int lr_mcmc_warnings(lr_engine* e, int32_t* warnings /* host */, void* stream);
 /* measurement hook: name of the kernel lr_mcmc_steps spends its time in, as a kernel trace prints it (n >= 64). */
 int lr_mcmc_describe(const lr_engine* e, char* buf /* host */, int32_t n);
+/* measurement hook: the four-chain kernel with helper waves exists once per configuration word - 0 = generic (reads the
+ * configuration at run time; also returned for every other kernel), 1 = models 0 / 1 and 2 = model 2 compiled in together
+ * with the default switches (const_rates 0, use_rate_HP on, poisson_HP 0, fractions 0 / 0.5); the same results bit for
+ * bit.  The environment variable LR_P4_GENERIC=1, read by lr_mcmc_init / lr_mcmc_restore, forces 0.  lr_mcmc_describe's name
+ * carries no word. */
+int lr_mcmc_p4_config(const lr_engine* e, int32_t* word /* host */);
 int lr_mcmc_destroy(lr_engine* e);
 
 #ifdef __cplusplus

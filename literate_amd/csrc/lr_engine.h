@@ -2,6 +2,7 @@
 // (lr_mcmc.hip: launch-based and two- / four-chain persistent kernels, lr_spec.hip: speculative team kernel,
 // lr_pack.hip: packing of the lineages for the persistent scans).
 #pragma once
+#include <cmath>
 #include "lr_internal.h"
 #include "lr_scan.h"
 #include "lr_step.h"
@@ -43,6 +44,7 @@ struct lr_engine {
     lr_p4_shares p4;          // per scanner wave: trips more (+) or fewer (-) than the equal share (four-chain kernel)
     bool p4_help;             // four-chain kernel: the form with helper waves - latched by lr_set_shares (init / restore), so
                               // that the form, its shares and the sums carried between launches belong together for a whole run
+    int p4_cfg;               // ... and its configuration word (LR_P4_CFG_*, lr_p4_cfg_choice), latched with p4_help
     bool packed_scan;         // launch-based engine whose scan kernel reads the PACKED lineages (lr_packscan.hip) instead of ts / te:
                               // planned by lr_mcmc_query_layout (lay.packed_scan), dropped by init / restore if the packing
                               // refuses the input (unsorted beyond LR_MAX_RUNS runs)
@@ -101,6 +103,20 @@ static inline bool lr_p4_help_choice(const lr_engine* e) {
     const char* env = getenv("LR_P4_HELP");
     if (e->lay.persistent != 2 || e->plan.unit == LR_TAB_PAIRGEN || e->cfg.sampler != 0 || e->plan.H > 264) return false;
     return env ? atoi(env) != 0 : true;
+}
+
+// Four-chain kernel with helper waves: the configuration word of the instantiation an engine runs (LR_P4_CFG_*, lr_step.h).
+// A specialised word needs the default switches - const_rates == 0, use_rate_HP != 0, poisson_HP == 0, in-bin fractions
+// (+0.0, 0.5) - and model 0, 1 (LR_P4_CFG_BDI) or 2 (LR_P4_CFG_KEIDING); model 3 and every other setting run the generic
+// instantiation, and LR_P4_GENERIC = 1 forces it (A/B runs, the bit-equality test).  Evaluated where lr_p4_help_choice is.
+static inline int lr_p4_cfg_choice(const lr_engine* e) {
+    const char* env = getenv("LR_P4_GENERIC");
+    if (!lr_p4_help_choice(e) || (env && atoi(env) != 0)) return LR_P4_CFG_GENERIC;
+    const lr_mcmc_config& c = e->cfg;
+    if (c.const_rates != 0 || c.use_rate_HP == 0 || c.poisson_HP != 0.0) return LR_P4_CFG_GENERIC;
+    if (c.frac_birth != LR_P4_FRAC_BIRTH || std::signbit(c.frac_birth) || c.frac_death != LR_P4_FRAC_DEATH) return LR_P4_CFG_GENERIC;
+    if (c.model == LR_MODEL_BD || c.model == LR_MODEL_ID) return LR_P4_CFG_BDI;
+    return c.model == LR_MODEL_KEIDING ? LR_P4_CFG_KEIDING : LR_P4_CFG_GENERIC;
 }
 
 // Which instantiation of the speculative kernel an engine runs (lr_spec.h): 0 = a team per pair; a team per chain: 1 = in

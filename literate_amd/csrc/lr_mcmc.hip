@@ -9,6 +9,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <new>
+#include <type_traits>
 
 #include "lr_chain.h"
 #include "lr_dd.h"
@@ -226,7 +227,8 @@ typedef __attribute__((address_space(3))) int lr_lds_i32;
 // parametric samplers' only (four-chain kernel: the launch picks the instantiation - a stepper function that carries one
 // step is a third smaller, and the kernel's instruction footprint is shared by two CUs' instruction cache)
 // HAND: the proposal's tables are built by a helper wave from the segments this wave hands over (`hand`, epoch `hand_epoch`)
-template <int PB, int ES, bool PRE = false, int SAMPLER = -1, bool HAND = false>
+// CFG: the four-chain kernel's configuration word (LR_P4_CFG_*, lr_step.h)
+template <int PB, int ES, bool PRE = false, int SAMPLER = -1, bool HAND = false, int CFG = LR_P4_CFG_GENERIC>
 __device__ __forceinline__ void lr_persist_step_body(const __attribute__((address_space(3))) lr_step_args* a3, int c, int lane,
                                                      __attribute__((address_space(3))) lr_seg_scratch* scratch3,
                                                      lr_lds_f64* st_f64, lr_lds_i32* st_i32, double lik, lr_lds_f64* table3,
@@ -244,7 +246,7 @@ __device__ __forceinline__ void lr_persist_step_body(const __attribute__((addres
     else if (PRE) {
         lr_rj_draws pre;
         lr_draws_load(draws, pre, lane);
-        lr_chain_step_core<true, PB, HAND>(st, a, 0, c, lane, (lr_seg_scratch*)scratch3, lik, reinterpret_cast<double2*>((double*)table3),
+        lr_chain_step_core<true, PB, HAND, CFG>(st, a, 0, c, lane, (lr_seg_scratch*)scratch3, lik, reinterpret_cast<double2*>((double*)table3),
                                            table_es, br_lds, br_lds + LR_H_WIDE, &pre, hand, hand_epoch);
     } else
         lr_chain_step_core<true, PB>(st, a, 0, c, lane, (lr_seg_scratch*)scratch3, lik, reinterpret_cast<double2*>((double*)table3),
@@ -294,7 +296,7 @@ __device__ __attribute__((noinline)) void lr_persist_step(const __attribute__((a
 //   st_f64 / st_i32: the four chains' state rows; red: [pair][wave][chain of the pair] scan sums; tab: the two pair
 //   tables, tab_doubles apart
 //   HELP: waves 2, 3 are helper waves - hands[wave] is this stepper's hand-over to wave 2 + wave (lr_persist4_kernel)
-template <int PB, int ES, int NW, int SAMPLER, bool HELP>
+template <int PB, int ES, int NW, int SAMPLER, bool HELP, int CFG = LR_P4_CFG_GENERIC>
 __device__ __attribute__((noinline)) void lr_persist4_steppers(const __attribute__((address_space(3))) lr_step_args* a3, int c0,
                                                                int n_chains, int wave, int lane,
                                                                __attribute__((address_space(3))) lr_seg_scratch* scratch3,
@@ -303,6 +305,7 @@ __device__ __attribute__((noinline)) void lr_persist4_steppers(const __attribute
                                                                const lr_draw_slot* draws /* [4]: made ahead (RJ sampler) */,
                                                                lr_table_hand* hands /* [2] */) {
     static_assert(!HELP || (ES == 2 && SAMPLER == 0), "helper waves: RJ sampler at unit resolution");
+    static_assert(CFG == LR_P4_CFG_GENERIC || HELP, "a configuration word comes with the helper waves");
     for (long long iter = 0; iter < n_iters; ++iter) {
 #pragma unroll 1
         for (int ph = 0; ph < 2; ++ph) {
@@ -314,7 +317,7 @@ __device__ __attribute__((noinline)) void lr_persist4_steppers(const __attribute
                 double lik = 0.0;
 #pragma unroll
                 for (int w2 = 2; w2 < (ES == 2 /* unit resolution: the block's sums in slot 2 */ ? 3 : NW); ++w2) lik += red[(ph * NW + w2) * 2 + wave];
-                lr_persist_step_body<PB, ES, ES == 2 /* unit resolution: draws made ahead */ && SAMPLER == 0, SAMPLER, HELP>(
+                lr_persist_step_body<PB, ES, ES == 2 /* unit resolution: draws made ahead */ && SAMPLER == 0, SAMPLER, HELP, CFG>(
                     a3, c, lane, scratch3, st_f64 + (2 * ph + wave) * (LR_STATE_ROWS * LR_ROW),
                     st_i32 + (2 * ph + wave) * (LR_ISTATE_ROWS * LR_ROW), lik, tab + ph * tab_doubles + wave, br3,
                     draws + (2 * ph + wave), HELP ? hands + wave : nullptr, (int)((2 * iter + ph + 1) & 0x3fffffff));
@@ -497,14 +500,20 @@ __global__ __launch_bounds__(T, LR_PERSIST_MINWAVES) void lr_persist_kernel(
 // and every SIMD carries one wave of the step and three scanners.  Before the hand-over arrives a helper scores the first
 // groups of the scan (sh.help_trips trips of the 128 helper lanes; the scanners stride over the rest), and the draws of the
 // OTHER pair's next step are one Philox call on each of the two oldest scanner waves (four waves, a call each, otherwise).
+// CFG (HELP only): the configuration word (LR_P4_CFG_*, lr_step.h).  The role waves - steppers, helpers' table duty, the
+// draw duty - are one wave's instruction stream per chain step and sit on the oldest wave of every SIMD, so what they
+// issue is taken from the scanners beside them as well; a specialised word compiles the run's model class and the default
+// switches into them as constants (constant propagation only: the same floating-point operations in the same order as
+// LR_P4_CFG_GENERIC executes for that configuration).  The launch picks the word (lr_p4_cfg_choice).
 template <int H, bool GENERAL, bool PARAM /* a parametric sampler's chain step (DDRate, trend_rate) instead of the RJ sampler's */,
-          bool HELP = false>
+          bool HELP = false, int CFG = LR_P4_CFG_GENERIC>
 __global__ __launch_bounds__(LR_P4_THREADS, LR_P4_THREADS / 256) void lr_persist4_kernel(const lr_step_args* __restrict__ ap /* in global memory: a by-value argument struct measured
                                                                        0.2 us per launch faster, but one instantiation then kept a copy of it in scratch
                                                                        memory and read its fields from there in every phase */,
                                                                        lr_packed_lineages pk, long long n8,
                                                                        lr_p4_shares sh, long long n_iters, char* carry_all) {
     static_assert(!HELP || (!GENERAL && !PARAM), "helper waves: RJ sampler at unit resolution");
+    static_assert(CFG == LR_P4_CFG_GENERIC || (HELP && H <= 264), "a configuration word comes with the helper waves");
     const lr_step_args& a = *ap;
     LR_PSTAMP(0);      // entry (LR_DIAG: wall-clock stamps of a launch's stages, blocks < 64; scratch/diag_p4_launch.py)
     constexpr int NW = LR_P4_THREADS / LR_WAVE;          // 16 waves: 2 steppers + 14 scanners (HELP: 2 + 2 helpers + 12)
@@ -557,7 +566,7 @@ __global__ __launch_bounds__(LR_P4_THREADS, LR_P4_THREADS / 256) void lr_persist
         const unsigned long long it = ((unsigned long long)(unsigned int)I[LR_I_IT_HI] << 32 | (unsigned int)I[LR_I_IT_LO]) + 1ull;
         lr_draw_slot* slot = &draws[ch];
         // (HELP: one wave per chain, one Philox call for both parts)
-        if (HELP) lr_spec_draw_both(a_lds, (int)(blockIdx.x * 4) + ch, lane, it, slot);
+        if (HELP) lr_spec_draw_both<CFG>(a_lds, (int)(blockIdx.x * 4) + ch, lane, it, slot);
         else lr_spec_draw_part(a_lds, (int)(blockIdx.x * 4) + ch, lane, it, slot, q >> 1);
     };
     // a helper wave's table duty of a phase whose steppers advance pair `ph`: once the stepper has handed them over, the
@@ -578,9 +587,15 @@ __global__ __launch_bounds__(LR_P4_THREADS, LR_P4_THREADS / 256) void lr_persist
         const lr_seg_scratch* sc = &scratch[k];
         const int eL = lane <= LR_KMAX ? sc->edge[0][lane] : 0, eM = lane <= LR_KMAX ? sc->edge[1][lane] : 0;
         double* tabd = reinterpret_cast<double*>(tab[ph]) + k;
+        // the builder's model, table size and in-bin fractions: read from the configuration, or the word's constants
+        int model = a_lds.cfg.model;
+        if (CFG == LR_P4_CFG_BDI) __builtin_assume((unsigned int)model < 2u);     // (lr_p4_cfg_choice: model 0 or 1)
+        if (CFG == LR_P4_CFG_KEIDING) model = LR_MODEL_KEIDING;
+        constexpr bool fixed = CFG != LR_P4_CFG_GENERIC;
         const double constP = lr_build_tables_segments<(H <= 264 ? lr_bins_per_lane(H) : 1), 2>(
-            sc, eL, eM, hand->KL, hand->KM, br_lds[0], br_lds[1], a_lds.cfg.model, a_lds.cfg.n_bins, a_lds.n_cls, a_lds.H,
-            reinterpret_cast<double2*>(tabd), lane, LR_TAB_UNIT, a_lds.cfg.frac_birth, a_lds.cfg.frac_death, ES, nullptr);
+            sc, eL, eM, hand->KL, hand->KM, br_lds[0], br_lds[1], model, a_lds.cfg.n_bins, a_lds.n_cls, fixed ? H : a_lds.H,
+            reinterpret_cast<double2*>(tabd), lane, LR_TAB_UNIT, fixed ? LR_P4_FRAC_BIRTH : a_lds.cfg.frac_birth,
+            fixed ? LR_P4_FRAC_DEATH : a_lds.cfg.frac_death, ES, nullptr);
         LR_WAVE_LDS_ORDER();
         lr_pair_planes_wave(tabd, H, a_lds.cfg.n_bins, lane, 0);
         if (lane == 0) st_f64[ch][LR_ROW_SCALARS * LR_ROW + LR_S_CONST_P] = constP;
@@ -648,7 +663,11 @@ __global__ __launch_bounds__(LR_P4_THREADS, LR_P4_THREADS / 256) void lr_persist
     // ([0, nh): helper waves, the rest: the scanner waves)
     const long long nh = HELP ? (long long)sh.help_trips * (2 * LR_WAVE) : 0;
     const long long n8w = any_shift ? (long long)k_mine * LR_P4_SCANNERS : n8 - nh;
-    auto help_scan = [&](int pr) {
+    // (the pair is a compile-time constant at every call, as it is in the scanners' unrolled loop: the table's LDS address
+    // then sits in the offset field of the slice's gathers - indexed by a run-time phase, each of the eight gathers of a
+    // trip took a vector add with the table base first)
+    auto help_scan = [&](auto pr_) {
+        constexpr int pr = decltype(pr_)::value;
         double s0 = 0.0, s1 = 0.0;
         if (nh > 0) lr_persist_scan<H, GENERAL, 1, false, false>(reinterpret_cast<const char*>(tab[pr]), pk, 0, nh, tid - 2 * LR_WAVE, 2 * LR_WAVE, &s0, &s1);
         leave_sums(pr, s0, s1);
@@ -671,7 +690,7 @@ __global__ __launch_bounds__(LR_P4_THREADS, LR_P4_THREADS / 256) void lr_persist
         lr_scan_drain(tail);
         prologue_draws();
     }
-    if (helper && !carried) help_scan(0);
+    if (helper && !carried) help_scan(std::integral_constant<int, 0>());
     __syncthreads();
     LR_PSTAMP(3);      // prologue done: pair 0's sums (scanned or carried), the first draws
     // phase ph of an iteration: the steppers advance pair `ph`, the scanners score pair `1 - ph`
@@ -682,7 +701,8 @@ __global__ __launch_bounds__(LR_P4_THREADS, LR_P4_THREADS / 256) void lr_persist
 #ifdef LR_DIAG
                 const unsigned long long dq0 = wall_clock64();
 #endif
-                help_scan(1 - ph);
+                if (ph == 0) help_scan(std::integral_constant<int, 1>());
+                else help_scan(std::integral_constant<int, 0>());
                 help_duty(ph, (int)((2 * iter + ph + 1) & 0x3fffffff));
 #ifdef LR_DIAG
                 const unsigned long long dq1 = wall_clock64();
@@ -697,7 +717,7 @@ __global__ __launch_bounds__(LR_P4_THREADS, LR_P4_THREADS / 256) void lr_persist
             }
         }
     } else if (!scanner)
-        lr_persist4_steppers<(H <= 264 ? lr_bins_per_lane(H) : 0), ES, NW, PARAM ? 1 : 0, HELP>(
+        lr_persist4_steppers<(H <= 264 ? lr_bins_per_lane(H) : 0), ES, NW, PARAM ? 1 : 0, HELP, CFG>(
             (const __attribute__((address_space(3))) lr_step_args*)&a_lds, c0, C, wave, lane,
             (__attribute__((address_space(3))) lr_seg_scratch*)&scratch[wave], (lr_lds_f64*)&st_f64[0][0], (lr_lds_i32*)&st_i32[0][0],
             (lr_lds_f64*)&red[0][0][0], (lr_lds_f64*)reinterpret_cast<double*>(tab[0]), 2 * LR_UNIT_PLANES * H,
@@ -1305,6 +1325,7 @@ extern "C" int lr_mcmc_create(const lr_mcmc_config* cfg, const double* ts, const
     for (int j = 0; j < 16; ++j) e->p4.delta[j] = 0;
     e->p4.n_slots = 8;
     e->p4_help = lr_p4_help_choice(e);                  // (lr_mcmc_describe before init; latched again by lr_set_shares)
+    e->p4_cfg = lr_p4_cfg_choice(e);
     e->streaming = false;
     e->packed_scan = lay.packed_scan != 0;
     e->fork = nullptr;
@@ -1663,7 +1684,11 @@ extern "C" int lr_mcmc_steps(lr_engine* e, int64_t n_iters, void* stream_) {
         if (general && param) hipLaunchKernelGGL((lr_persist4_kernel<HH, true, true>), g4, b4, 0, stream, ap, pk, e->n8, e->p4, (long long)n, p4_carry);   \
         else if (general) hipLaunchKernelGGL((lr_persist4_kernel<HH, true, false>), g4, b4, 0, stream, ap, pk, e->n8, e->p4, (long long)n, p4_carry);      \
         else if (param) hipLaunchKernelGGL((lr_persist4_kernel<HH, false, true>), g4, b4, 0, stream, ap, pk, e->n8, e->p4, (long long)n, p4_carry);        \
-        else if (e->p4_help)      /* (helper waves: H <= 264, lr_p4_help_choice) */                                           \
+        else if (e->p4_help && e->p4_cfg == LR_P4_CFG_BDI)      /* (helper waves: H <= 264, lr_p4_help_choice; the word: lr_p4_cfg_choice) */ \
+            hipLaunchKernelGGL((lr_persist4_kernel<(HH <= 264 ? HH : 264), false, false, true, LR_P4_CFG_BDI>), g4, b4, 0, stream, ap, pk, e->n8, e->p4, (long long)n, p4_carry); \
+        else if (e->p4_help && e->p4_cfg == LR_P4_CFG_KEIDING)                                                                \
+            hipLaunchKernelGGL((lr_persist4_kernel<(HH <= 264 ? HH : 264), false, false, true, LR_P4_CFG_KEIDING>), g4, b4, 0, stream, ap, pk, e->n8, e->p4, (long long)n, p4_carry); \
+        else if (e->p4_help)                                                                                                  \
             hipLaunchKernelGGL((lr_persist4_kernel<(HH <= 264 ? HH : 264), false, false, true>), g4, b4, 0, stream, ap, pk, e->n8, e->p4, (long long)n, p4_carry); \
         else hipLaunchKernelGGL((lr_persist4_kernel<HH, false, false>), g4, b4, 0, stream, ap, pk, e->n8, e->p4, (long long)n, p4_carry);                  \
     } else if (wide) {                                                                                                        \
@@ -1751,7 +1776,15 @@ extern "C" int lr_mcmc_warnings(lr_engine* e, int32_t* warnings, void* stream_) 
     return (int)he;
 }
 
-// name of the kernel lr_mcmc_steps spends its time in, as rocprofv3's kernel trace prints it (without arguments)
+// configuration word of the four-chain kernel an engine runs (0 = the generic instantiation, or another kernel)
+extern "C" int lr_mcmc_p4_config(const lr_engine* e, int32_t* word) {
+    if (!e || !word) return LR_ERR_NULL;
+    *word = (e->persistent && e->lay.persistent == 2 && e->p4_help) ? e->p4_cfg : LR_P4_CFG_GENERIC;
+    return LR_OK;
+}
+
+// name of the kernel lr_mcmc_steps spends its time in, as rocprofv3's kernel trace prints it (without arguments; the
+// four-chain kernel: without its configuration word, which lr_mcmc_p4_config tells)
 extern "C" int lr_mcmc_describe(const lr_engine* e, char* buf, int32_t n) {
     if (!e || !buf) return LR_ERR_NULL;
     if (n < 64) return LR_ERR_SIZE;

@@ -27,6 +27,18 @@ struct lr_step_args {
     unsigned int* warn;     // engine warning word (LR_WARN_*), beside the status word
 };
 
+// Configuration word of the four-chain kernel with helper waves (lr_persist4_kernel's CFG): what a run's lr_mcmc_config
+// fixes for the whole run, as a compile-time constant of the stepper waves' function, the helper waves' table duty and the
+// draw duty.  A specialised word stands for the default switches - const_rates == 0, use_rate_HP != 0, poisson_HP == 0,
+// frac_birth == 0, frac_death == 0.5 - and a model class; the code under it is the generic code with those reads of cfg.*
+// replaced by their values (the same floating-point operations on the same values in the same order, dead branches gone).
+// Every other setting runs LR_P4_CFG_GENERIC, which reads the configuration at run time (lr_p4_cfg_choice, lr_engine.h).
+#define LR_P4_CFG_GENERIC 0
+#define LR_P4_CFG_BDI 1        /* models 0, 1: the BDI partial likelihood (which of the two stays a run-time value) */
+#define LR_P4_CFG_KEIDING 2    /* model 2 */
+#define LR_P4_FRAC_BIRTH 0.0   /* the in-bin fractions of year-resolution input, as the specialised words assume them */
+#define LR_P4_FRAC_DEATH 0.5
+
 // where chain c's lookup table starts.  General layout: chain-major, tab_stride double2 per chain.
 // Unit-resolution layout: groups of cb chains, inside a group [pair][2H] double2 = (even chain, odd chain);
 // the returned pointer addresses this chain's component, consecutive entries are 2 doubles apart.
@@ -588,6 +600,8 @@ __device__ __forceinline__ double lr_wave_multiplier_pre(double& R, int K, bool 
 // the same draws by ONE wave in ONE Philox call, addressed as lr_propose_rj addresses them when it draws by itself: lanes
 // 0..31 the multiplier pairs of their rates, lanes LR_UD_LANE + 0..3 the wave-uniform ones (the four-chain kernel with
 // helper waves: the kernel is bound by its vector instruction count, a Philox block is ~100 instructions)
+// CFG: the kernel's configuration word (LR_P4_CFG_*)
+template <int CFG = LR_P4_CFG_GENERIC>
 __device__ __forceinline__ void lr_spec_draw_both(const lr_step_args& a, int c, int lane, unsigned long long it, lr_draw_slot* out) {
     const lr_mcmc_config& cfg = a.cfg;
     const lr_stream rng{(uint32_t)cfg.seed, (uint32_t)(cfg.chain_offset + c)};
@@ -599,7 +613,7 @@ __device__ __forceinline__ void lr_spec_draw_both(const lr_step_args& a, int c, 
     const double lu = lr_log(ul == 0 ? u.a : 1.0);
     const double r_a = lr_bcast(u.a, LR_UD_LANE + 1), q_b = lr_bcast(u.b, LR_UD_LANE + 2);
     double beta = 0.0;
-    if (!(r_a < 0.8) && r_a < 0.999 && cfg.const_rates == 0 && q_b > 0.5) {
+    if (!(r_a < 0.8) && r_a < 0.999 && (CFG != LR_P4_CFG_GENERIC || cfg.const_rates == 0) && q_b > 0.5) {
         double ga, gb;
         lr_wave_gamma2(rng, it, LR_P_BETA_A, LR_SHAPE_BETA_RJ, LR_P_BETA_B, LR_SHAPE_BETA_RJ, lane, &ga, &gb);
         beta = ga / (ga + gb);
@@ -641,7 +655,9 @@ struct lr_table_hand {
 // handed over (epoch `hand_epoch`), this wave goes on with the guard and the prior and leaves the column, its pair planes,
 // the model constant and the rank cache of the proposal to the helper (p.table_by_helper) - this instance then holds no
 // table builder at all.  base_col is then the base state's whole table, `col_doubles` entries CS doubles apart.
-template <bool LDS_CONSTS = false, int PB = 0, int CS = 2, bool PAIR_PLANES = true, bool HAND = false>
+// CFG (four-chain kernel with helper waves): its configuration word - a specialised one fixes the switches the moves read
+// (LR_P4_CFG_*: const_rates == 0, use_rate_HP != 0, poisson_HP == 0); the tables are the helper's then.
+template <bool LDS_CONSTS = false, int PB = 0, int CS = 2, bool PAIR_PLANES = true, bool HAND = false, int CFG = LR_P4_CFG_GENERIC>
 __device__ __forceinline__ void lr_propose_rj(const lr_step_args& a, int c, int lane, lr_seg_scratch* scratch_p,
                                               uint64_t it, lr_rj_state& s, lr_rj_prop& p, double2* table,
                                               int table_es, const lr_rj_draws* pre = nullptr,
@@ -650,8 +666,10 @@ __device__ __forceinline__ void lr_propose_rj(const lr_step_args& a, int c, int 
                                               lr_table_hand* hand = nullptr, int hand_epoch = 0) {
     static_assert(CS == 2 || (PB > 0 && !PAIR_PLANES), "a column of its own: one-pass builder, no pair planes");
     static_assert(!HAND || PB > 0, "a helper wave runs the one-pass builder");
+    static_assert(CFG == LR_P4_CFG_GENERIC || HAND, "a configuration word comes with the helper waves");
     lr_seg_scratch& scratch = *scratch_p;
     const lr_mcmc_config& cfg = a.cfg;
+    constexpr bool fixed = CFG != LR_P4_CFG_GENERIC;     // the default switches as constants
     const int n_bins = cfg.n_bins;
     const lr_stream rng{(uint32_t)cfg.seed, (uint32_t)(cfg.chain_offset + c)};
     const double L = s.L, M = s.M, tL = s.tL, tM = s.tM;
@@ -707,7 +725,7 @@ __device__ __forceinline__ void lr_propose_rj(const lr_step_args& a, int c, int 
             peM = lr_wave_edges(tM, 0);
             move_kind = 3;
         }
-    } else if (r.a < 0.999 && cfg.const_rates == 0) {
+    } else if (r.a < 0.999 && (fixed || cfg.const_rates == 0)) {
         // RJMCMC (LRF:71-97)
         move_kind = 4;
         const lr_u2 q = pre ? lr_u2{pre->q_a, pre->q_b} : lr_u2{lr_bcast(ud.a, LR_UD_LANE + 2), lr_bcast(ud.b, LR_UD_LANE + 2)};
@@ -749,14 +767,14 @@ __device__ __forceinline__ void lr_propose_rj(const lr_step_args& a, int c, int 
         // Gibbs draws of the hyper-parameters (LRF:283-287, 99-108, 210-213)
         move_kind = 5;
         double gl = 0.0, gm = 0.0, gp = 0.0, dummy;
-        if (cfg.use_rate_HP)
+        if (fixed || cfg.use_rate_HP)
             lr_wave_gamma2(rng, it, LR_P_GIBBS_L, LR_HP_GAMMA_SHAPE + LR_GAMMA_SHAPE * KL, LR_P_GIBBS_M,
                            LR_HP_GAMMA_SHAPE + LR_GAMMA_SHAPE * KM, lane, &gl, &gm);
-        if (cfg.poisson_HP == 0.0)
+        if (fixed || cfg.poisson_HP == 0.0)
             lr_wave_gamma2(rng, it, LR_P_GIBBS_POI, LR_RJHP_SHAPE + KL + KM, LR_P_GIBBS_POI, LR_RJHP_SHAPE + KL + KM, lane,
                            &gp, &dummy);
-        if (cfg.poisson_HP == 0.0) poi = gp * (1. / (LR_RJHP_RATE + 2));
-        if (cfg.use_rate_HP) {
+        if (fixed || cfg.poisson_HP == 0.0) poi = gp * (1. / (LR_RJHP_RATE + 2));
+        if (fixed || cfg.use_rate_HP) {
             const double sL = lr_wave_sum(lane < KL ? L : 0.0), sM = lr_wave_sum(lane < KM ? M : 0.0);
             g0 = gl * (1. / (LR_HP_GAMMA_RATE + sL));
             g1 = gm * (1. / (LR_HP_GAMMA_RATE + sM));
@@ -848,7 +866,8 @@ __device__ __forceinline__ void lr_propose_rj(const lr_step_args& a, int c, int 
 // caller knows the proposal to be neither a Gibbs step nor invalid, and sets LR_S_LIK_P once the scan's sums are in)
 // HAND (four-chain kernel with helper waves): the proposal's lookup tables, pair planes and model constant are another
 // wave's (lr_propose_rj's HAND) - the scalar LR_S_CONST_P of the state then belongs to that wave, see lr_chain_store_handed
-template <bool LDS_CONSTS = false, int PB = 0, bool HAND = false>
+// CFG: the four-chain kernel's configuration word (LR_P4_CFG_*), for the proposal
+template <bool LDS_CONSTS = false, int PB = 0, bool HAND = false, int CFG = LR_P4_CFG_GENERIC>
 __device__ __forceinline__ void lr_chain_step_core(lr_chain_regs& st, const lr_step_args& a, int mode, int c, int lane,
                                                    lr_seg_scratch* scratch_p, double lik_sum, double2* table,
                                                    int table_es = 2, const double* br_lds = nullptr,
@@ -912,7 +931,7 @@ __device__ __forceinline__ void lr_chain_step_core(lr_chain_regs& st, const lr_s
 
     // ---- propose iteration `it` (LRF:234-304) ----
     lr_rj_prop p;
-    if (HAND) lr_propose_rj<LDS_CONSTS, (PB > 0 ? PB : 1), 2, true, HAND>(a, c, lane, scratch_p, it, s, p, table, table_es, pre, br_lds, logbr_lds, nullptr, 0, 0.0, hand, hand_epoch);
+    if (HAND) lr_propose_rj<LDS_CONSTS, (PB > 0 ? PB : 1), 2, true, HAND, CFG>(a, c, lane, scratch_p, it, s, p, table, table_es, pre, br_lds, logbr_lds, nullptr, 0, 0.0, hand, hand_epoch);
     else lr_propose_rj<LDS_CONSTS, PB>(a, c, lane, scratch_p, it, s, p, table, table_es, pre, br_lds, logbr_lds);
 
     // ---- back into the state registers ----

@@ -257,6 +257,13 @@ class ChainEngine:
         _hip.check(self.lib.lr_mcmc_describe(self.handle, buf, 128), "lr_mcmc_describe")
         return buf.value.decode()
 
+    def p4_config(self):
+        """Configuration word of the four-chain kernel steps() runs: 0 = the generic instantiation (or another kernel),
+        1 = models 0 / 1, 2 = model 2 with the default switches compiled in (LR_P4_GENERIC=1 at init() forces 0)."""
+        w = C.c_int32(0)
+        _hip.check(self.lib.lr_mcmc_p4_config(self.handle, C.byref(w)), "lr_mcmc_p4_config")
+        return int(w.value)
+
     def timed_steps(self, n):
         """steps(n) bracketed by HIP events on the launch stream; returns elapsed device ms (blocks)."""
         ms = C.c_float(0.0)
