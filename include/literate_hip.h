@@ -452,7 +452,13 @@ typedef struct lr_mcmc_config {
     /* unit-resolution data: 1 asserts that EVERY lineage has ts - floor(ts) == frac_birth and
      * te - (ceil(te) - 1) == frac_death (true for year-resolution input + death_jitter, i.e. every
      * dataset the reference ships: 0 and 0.5).  The fractions are then folded into the lookup
-     * tables (8-byte entries, half the LDS traffic per lineage).  0 = general times.            */
+     * tables (8-byte entries, half the LDS traffic per lineage).  0 = general times.
+     * frac_birth in [0, 1), frac_death in (0, 1]: any shared pair is taken as it is (-death_jitter 0.25 gives
+     * (0, 0.25)); frac_death == 1 is integer te (-death_jitter 0 or 1): a death ON a window edge belongs to the bin
+     * it closes, and a lineage with te == ts gathers the death entry of the bin BEFORE its birth bin (entry 0, which
+     * is 0, when born in the first bin).  The fractions never steer the choice of kernel; only the four-chain
+     * kernel's specialised configuration words assume (+0.0, 0.5) and every other pair runs its generic one
+     * (tests/test_hip_shared_fractions.py).                                                             */
     int32_t unit_resolution;
     int32_t engine_mode;      /* 0 = auto, 1 = launch-per-iteration engine (fused, pipelined), 2 = a persistent kernel
                                * (the library picks which), 3 = four chains per block, 4 = two chains per block,

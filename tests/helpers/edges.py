@@ -105,21 +105,24 @@ def engine_runs(engine, model, sampler, unit, n_bins):
     return engine in ("persistent4", "packed")
 
 
-def make_config(model, sampler, unit, n_bins, n_chains, n_lineages, engine_mode):
+def make_config(model, sampler, unit, n_bins, n_chains, n_lineages, engine_mode, frac_birth=0.0, frac_death=0.5):
+    """(frac_birth, frac_death): the shared in-bin fractions of unit-resolution data, (0, 0.5) for year-resolution input with
+    the default death_jitter; general times carry none."""
     from literate_amd import _hip
     end = float(n_bins) + 0.5
     return _hip.McmcConfig(
         n_lineages=int(n_lineages), n_bins=int(n_bins), n_chains=int(n_chains), model=int(model), use_rate_HP=1,
         s_freq=10, n_trace_slots=4, update_fraction=0.75, t0=0.0, start_time=0.0, end_time=end, seed=1,
-        unit_resolution=int(unit), engine_mode=int(engine_mode), frac_birth=0.0, frac_death=0.5 if unit else 0.0, sampler=int(sampler), m_birth=2 if sampler == 1 else 0,
+        unit_resolution=int(unit), engine_mode=int(engine_mode), frac_birth=float(frac_birth) if unit else 0.0,
+        frac_death=float(frac_death) if unit else 0.0, sampler=int(sampler), m_birth=2 if sampler == 1 else 0,
         m_death=2 if sampler == 1 else 0, dd_present=end if sampler == 1 else 0.0, dd_init_death=0.1)
 
 
-def query(model, sampler, unit, n_bins, n_chains, n_lineages, engine_mode, cus=256):
+def query(model, sampler, unit, n_bins, n_chains, n_lineages, engine_mode, cus=256, frac_birth=0.0, frac_death=0.5):
     """lr_mcmc_query_layout on the host (no device needed), LR_DEVICE_CUS pinned: (rc, layout)."""
     from literate_amd import _hip
     lib = _hip.load()
-    cfg = make_config(model, sampler, unit, n_bins, n_chains, n_lineages, engine_mode)
+    cfg = make_config(model, sampler, unit, n_bins, n_chains, n_lineages, engine_mode, frac_birth, frac_death)
     lay = _hip.McmcLayout()
     old = os.environ.get("LR_DEVICE_CUS")
     os.environ["LR_DEVICE_CUS"] = str(cus)
@@ -233,3 +236,179 @@ def instantiated_cells():
                     if instantiated(cell):
                         out.add(cell)
     return out
+
+
+# ---- shared by the oracle comparisons of tests/test_hip_edges.py and tests/test_hip_shared_fractions.py ----------------
+ORACLE_CHAINS = (0, 18, 36)       # of 37 chains: the first, a middle one, the ragged last block's
+
+
+def placed_lineages(n, rng):
+    """The lineages placed on purpose on n unit bins, as (birth year, death year) integer pairs - a lineage is born at its
+    birth year and dies `death_jitter` after its death year: one over the whole window, born in bin 0 and in the last
+    bin, dying in the last bin, 20 extant ones (model 3's extant block), a run of 21 lineages in one birth bin (its groups
+    split), and pairs dying d = 0..3 bins apart in the top bins (the largest 16-bit slot offsets of csrc/lr_pack.hip).
+    Draws 40 integers from rng."""
+    b = rng.integers(0, n, 40)
+    extra = [(0, n), (0, 0), (0, n - 1), (n - 1, n - 1), (n - 1, n)]
+    extra += [(int(x), n) for x in b[:20]]                                # extant
+    extra += [(int(x), n - 1) for x in b[20:]]                            # dying in the last bin
+    r = n // 2
+    extra += [(r, min(r + (k % 3), n - 1)) for k in range(21)]            # one birth bin, 21 lineages
+    top = max(0, n - 8)
+    for d in range(4):                                                    # pairs dying d bins apart in the top bins
+        extra += [(top, n - 1 - d), (top, n - 1)] * 2
+    return extra
+
+
+def rj_reference(ts, te, model, n_bins, seed, n_it, chains=ORACLE_CHAINS):
+    """Binned statistics of the data (the oracle's own binning) and the oracle trajectories of `chains`."""
+    from oracle import literate_oracle as lo
+    from oracle import mcmc_oracle as mo
+    t0, sp, ex, br = lo.bin_events_cli(ts, te)
+    assert t0 == 0 and len(sp) == n_bins
+    stats = dict(sp=sp, ex=ex, br=br)
+    if model == 3:
+        stats["ex_dead"], stats["br_dead"] = lo.bin_events_dead(ts, te, te.max())
+    refs = {}
+    for c in chains:
+        with np.errstate(all="ignore"):
+            refs[c] = mo.run_mcmc(stats, ts.min(), te.max(), mo.Settings(model_BDI=model), mo.PhiloxDraws(seed, c), n_it, 1,
+                                  k_max=32)["mcmc"]
+    return stats, refs
+
+
+def check_forced(engine, cell):
+    want = {"packed": "packed", "persistent2": "persist2", "persistent4": "persist4", "spec": "spec"}.get(engine)
+    if want:
+        assert cell[0] == want, (engine, cell)
+    if engine == "launch":
+        assert cell[0] == "launch", cell
+
+
+def reference_loglik(ts, te, lam, mu, model, stats, pre):
+    """fp64 log-likelihood of one accepted state on the raw times: the per-lineage form (models 0-2) or the binned
+    Keiding form with the death half on the lineages that die in the window (model 3)."""
+    from oracle import literate_oracle as lo
+    if model == 3:
+        return lo.calc_likelihood(3, lam, mu, stats)
+    return lo.per_lineage_loglik(ts, te, 0.0, lam, mu, model, stats["br"], pre=pre)
+
+
+def run_rj_against_the_oracle(eng, ts, te, model, n_bins, stats, refs, n_it, cell):
+    """n_it iterations of an RJ engine (s_freq 1) in two launches: the chains of refs (rj_reference) row by row against
+    oracle/mcmc_oracle.run_mcmc (iteration and K columns exact, the head at rtol = atol = 1e-9), and every chain's
+    accepted state re-scored in fp64 by the oracle on the raw times and by lr_bd_loglik_batch (rtol 1e-9)."""
+    from literate_amd import ops
+    from literate_amd.engine import split_trace_row
+    from oracle import literate_oracle as lo
+    C = eng.n_chains
+    eng.init()
+    eng.steps(n_it // 2)
+    eng.steps(n_it - n_it // 2)
+    tr = eng.trace_rows()
+    for c, ref in refs.items():
+        for i in range(n_it):
+            head, _, _ = split_trace_row(tr[i, c])
+            r = ref[i]
+            assert head[0] == r[0] and head[6] == r[6] and head[7] == r[7], (cell, c, i, head[:8], r[:8])
+            assert np.allclose(head[:13], r[:13], rtol=1e-9, atol=1e-9), (cell, c, i, head, r)
+    snap = eng.snapshot()
+    assert np.all(snap["it"] == n_it) and np.all(np.isfinite(snap["likA"]))
+    lam, mu = accepted_rates(snap, n_bins, C)
+    pre = lo.lineage_bins(ts, te, 0.0, n_bins)
+    ref = np.array([reference_loglik(ts, te, lam[c], mu[c], model, stats, pre) for c in range(C)])
+    assert np.allclose(snap["likA"], ref, rtol=1e-9, atol=0.0), (cell, snap["likA"] - ref)
+    lik = ops.bd_loglik_batch(eng.ts, eng.te, eng.t0, lam, mu, model, br_length=stats["br"],
+                              end_time=eng.end_time).cpu().numpy()
+    assert np.allclose(lik, snap["likA"], rtol=1e-9, atol=0.0), (cell, lik - snap["likA"])
+    return snap
+
+
+def fixed_point_bound(ts, te, lam, mu):
+    """Absolute bound of the pair-general tables' 32-bit in-bin fractions (csrc/lr_pack.hip), for one chain's state:
+    a birth fraction is rounded to the nearest 2^-32 (its group carries their exact sum: <= 2^-33 per lineage); a death
+    fraction likewise, but a PAIR carries the rounded mean of its two rounded fractions, which the doubled slope turns
+    back into their sum (<= 2^-33 + 2^-33 per lineage).  Each fraction multiplies the exposure rate of its bin, at most
+    (lambda + mu)max, so |error| <= 3 * 2^-33 * N * (lambda + mu)max, plus 64 ulp of the sum of |terms| for the fp64
+    summation order (1 % of the bound at these sizes)."""
+    R = float(np.max(lam + mu))
+    cum = float(np.sum(lam + mu))
+    terms = len(ts) * (np.max(np.abs(np.log(np.concatenate([lam, mu])))) + 2 * cum + 2 * R + 10.0)
+    return 3.0 * 2.0 ** -33 * len(ts) * R + 64 * 2.0 ** -52 * terms
+
+
+def param_stats(kind, ts, te, n_bins):
+    """create_bins statistics of the lineages and (trend) the covariate, binned by the oracle's own create_bins."""
+    from oracle import literate_oracle as lo
+    origin, present = float(ts.min()), float(te.max())
+    o, p, nsp, nex, dt, nb, t_range = lo.create_bins(origin, present, ts, te, 0)
+    assert nb == n_bins
+    trend = None
+    if kind == "trend":
+        x = np.arange(n_bins + 1, dtype=float)
+        trend = lo.normalise_trend(np.sin(x / 7.0) + 0.02 * x)
+        assert len(trend) == n_bins
+    return (o, p, nsp, nex, dt, t_range), trend
+
+
+def param_reference(kind, bins, trend, n_it, s, seed, off):
+    """The oracle loops of the parametric samplers (DDRate -mBirth 2 -mDeath 2, trend_rate) for ORACLE_CHAINS."""
+    from oracle import dd_mcmc_oracle as ddo
+    from oracle import trend_mcmc_oracle as tro
+    o, p, nsp, nex, dt, t_range = bins
+    with np.errstate(all="ignore"):
+        emp = (nsp / dt, nex / dt)
+    refs = {}
+    for c in ORACLE_CHAINS:
+        if kind == "dd":
+            refs[c] = ddo.run_dd_mcmc(nsp, nex, dt, t_range, o, p, 2, 2, ddo.PhiloxDraws(seed, off + c), n_it, s, emp=emp)
+        else:
+            refs[c] = tro.run_trend_mcmc(nsp, nex, dt, trend, tro.PhiloxDraws(seed, off + c), n_it, s, False, False, emp=emp)
+    return emp, refs
+
+
+def param_engine(kind, ts, te, trend, n_chains, engine, seed, s, n_slots, off):
+    from literate_amd.ddrate import DDRateEngine
+    from literate_amd.trendrate import TrendRateEngine
+    origin, present = float(ts.min()), float(te.max())
+    kw = dict(seed=seed, s_freq=s, n_trace_slots=n_slots, chain_offset=off, engine=engine)
+    if kind == "dd":
+        return DDRateEngine(ts, te, origin, present, n_chains, m_birth=2, m_death=2, **kw)
+    return TrendRateEngine(ts, te, origin, present, trend, n_chains, **kw)
+
+
+def param_rates(kind, snap, dt, trend, n_chains):
+    from literate_amd import ops
+    if kind == "dd":
+        args = np.stack([snap["L"][c][:8] for c in range(n_chains)])
+        b, d, _, _ = ops.dd_rates(args, dt, 2, 2)
+    else:
+        args = np.stack([snap["L"][c][:6] for c in range(n_chains)])
+        b, d = ops.trend_rates(args, trend, False, False)
+    return [x.cpu().numpy() for x in (b, d)]
+
+
+def run_param_against_the_oracle(eng, kind, ts, te, bins, trend, emp, refs, n_it, s, cell):
+    """n_it iterations of a parametric engine in two launches: the sampled log rows of ORACLE_CHAINS (scalars and per-bin
+    columns) against the oracle loops with the tolerances of test_ddrate_sampler_follows_oracle, and every chain's
+    accepted parameter vector re-scored by lr_bd_loglik_batch."""
+    from literate_amd import ops
+    o, p, nsp, nex, dt, t_range = bins
+    assert np.array_equal(eng.n_spec, nsp) and np.array_equal(eng.n_exti, nex) and np.allclose(eng.DT, dt, rtol=1e-13)
+    eng.init()
+    eng.steps(n_it // 2)
+    eng.steps(n_it - n_it // 2)
+    for c in ORACLE_CHAINS:
+        got = eng.log_rows(c, emp=emp)
+        ref = refs[c]
+        assert len(got) == len(ref) == n_it // s
+        for i, (g, r) in enumerate(zip(got, ref)):
+            assert g[0] == r[0]
+            assert np.allclose(g[1:-3], r[1:-3], rtol=1e-9, atol=1e-9, equal_nan=True), (cell, c, i, g[:14], r[:14])
+            assert np.allclose(g[-3:], r[-3:], rtol=1e-7, atol=1e-9, equal_nan=True)
+    snap = eng.snapshot()
+    assert np.all(snap["it"] == n_it)
+    b, d = param_rates(kind, snap, dt, trend, eng.n_chains)
+    lik = ops.bd_loglik_batch(ts, te, o, b, d, 2).cpu().numpy()
+    assert np.allclose(lik, snap["likA"], rtol=1e-9), (cell, lik - snap["likA"])
+    return snap
