@@ -631,6 +631,13 @@ int lr_mcmc_describe(const lr_engine* e, char* buf /* host */, int32_t n);
  * bit.  The environment variable LR_P4_GENERIC=1, read by lr_mcmc_init / lr_mcmc_restore, forces 0.  lr_mcmc_describe's name
  * carries no word. */
 int lr_mcmc_p4_config(const lr_engine* e, int32_t* word /* host */);
+/* measurement hook: the scanning lanes of the four-chain kernel with helper waves keep the decoded scan groups of their
+ * first trips in registers for a whole launch instead of loading and decoding them in every scan; the same results bit for
+ * bit.  out[0] = resident trips per scanner lane in use (the two scanner waves that also make the draws ahead keep fewer),
+ * out[1] = resident trips per helper lane, out[2] = packed groups, out[3] = the helper lanes' trips; out[0] = out[1] = 0 for
+ * every other kernel and under the environment variable LR_P4_RESIDENT=0, read by lr_mcmc_init / lr_mcmc_restore, which
+ * sends every trip through the scan loop. */
+int lr_mcmc_p4_resident(const lr_engine* e, int32_t out[4] /* host */);
 int lr_mcmc_destroy(lr_engine* e);
 
 #ifdef __cplusplus

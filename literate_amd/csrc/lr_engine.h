@@ -45,6 +45,7 @@ struct lr_engine {
     bool p4_help;             // four-chain kernel: the form with helper waves - latched by lr_set_shares (init / restore), so
                               // that the form, its shares and the sums carried between launches belong together for a whole run
     int p4_cfg;               // ... and its configuration word (LR_P4_CFG_*, lr_p4_cfg_choice), latched with p4_help
+    bool p4_resident;         // ... and whether its scanning lanes keep decoded groups in registers (lr_p4_resident_choice), latched with p4_help
     bool packed_scan;         // launch-based engine whose scan kernel reads the PACKED lineages (lr_packscan.hip) instead of ts / te:
                               // planned by lr_mcmc_query_layout (lay.packed_scan), dropped by init / restore if the packing
                               // refuses the input (unsorted beyond LR_MAX_RUNS runs)
@@ -117,6 +118,14 @@ static inline int lr_p4_cfg_choice(const lr_engine* e) {
     if (c.frac_birth != LR_P4_FRAC_BIRTH || std::signbit(c.frac_birth) || c.frac_death != LR_P4_FRAC_DEATH) return LR_P4_CFG_GENERIC;
     if (c.model == LR_MODEL_BD || c.model == LR_MODEL_ID) return LR_P4_CFG_BDI;
     return c.model == LR_MODEL_KEIDING ? LR_P4_CFG_KEIDING : LR_P4_CFG_GENERIC;
+}
+
+// Four-chain kernel with helper waves: the scanning lanes keep the decoded groups of their first trips in registers for a
+// whole launch (lr_persist4_kernel's NR, lr_resident_groups in lr_scan.h); LR_P4_RESIDENT = 0: every trip goes through the
+// scan loop (A/B runs, the bit-equality test).  Evaluated where lr_p4_help_choice is.
+static inline bool lr_p4_resident_choice(const lr_engine* e) {
+    const char* env = getenv("LR_P4_RESIDENT");
+    return lr_p4_help_choice(e) && !(env && atoi(env) == 0);
 }
 
 // Which instantiation of the speculative kernel an engine runs (lr_spec.h): 0 = a team per pair; a team per chain: 1 = in

@@ -259,7 +259,9 @@ __device__ __forceinline__ void lr_persist_step_body(const __attribute__((addres
 // End of a wave's share of scan number `scans_done` in the four-chain kernel: the lanes' sums into slot `slot` of
 // `part`, count in, and - the wave that arrives LAST of the NA scanning waves - add the block's sums up, per lane over the
 // slots in slot order, then across the lanes (the same order whoever is last), into out[0..1].
-template <int NA>
+// BATCH: the last arriver reads the slots BATCH at a time (the additions and their order are the same; a wave that keeps
+// resident scan groups has no room for all NA entries at once)
+template <int NA, int BATCH = NA>
 __device__ __forceinline__ void lr_p4_leave_sums(double2 (*part)[LR_WAVE], int* arrived, double* out, int slot, int lane,
                                                  int& scans_done, double s0, double s1) {
     part[slot][lane] = make_double2(s0, s1);
@@ -271,6 +273,7 @@ __device__ __forceinline__ void lr_p4_leave_sums(double2 (*part)[LR_WAVE], int* 
         double a0 = 0.0, a1 = 0.0;
 #pragma unroll
         for (int w = 0; w < NA; ++w) {
+            if (BATCH < NA && w > 0 && w % BATCH == 0) asm volatile("" : "+v"(a0), "+v"(a1) :: "memory");
             const double2 v = part[w][lane];
             a0 += v.x, a1 += v.y;
         }
@@ -296,7 +299,10 @@ __device__ __attribute__((noinline)) void lr_persist_step(const __attribute__((a
 //   st_f64 / st_i32: the four chains' state rows; red: [pair][wave][chain of the pair] scan sums; tab: the two pair
 //   tables, tab_doubles apart
 //   HELP: waves 2, 3 are helper waves - hands[wave] is this stepper's hand-over to wave 2 + wave (lr_persist4_kernel)
-template <int PB, int ES, int NW, int SAMPLER, bool HELP, int CFG = LR_P4_CFG_GENERIC>
+//   TAG: not used - the kernel's NR, so that the kernels with resident scan groups call instantiations of their own: the
+//   function is specialised for what its callers pass alike (LDS addresses among it), and a second caller of the
+//   instantiation of a kernel without resident groups would take that away from it
+template <int PB, int ES, int NW, int SAMPLER, bool HELP, int CFG = LR_P4_CFG_GENERIC, int TAG = 0>
 __device__ __attribute__((noinline)) void lr_persist4_steppers(const __attribute__((address_space(3))) lr_step_args* a3, int c0,
                                                                int n_chains, int wave, int lane,
                                                                __attribute__((address_space(3))) lr_seg_scratch* scratch3,
@@ -505,8 +511,23 @@ __global__ __launch_bounds__(T, LR_PERSIST_MINWAVES) void lr_persist_kernel(
 // issue is taken from the scanners beside them as well; a specialised word compiles the run's model class and the default
 // switches into them as constants (constant propagation only: the same floating-point operations in the same order as
 // LR_P4_CFG_GENERIC executes for that configuration).  The launch picks the word (lr_p4_cfg_choice).
+// NR (HELP only): > 0 = every scanner lane keeps the decoded groups of its first NR trips (LR_P4_NR_DRAW on the two waves
+// that also make the draws ahead), every helper lane those of its first LR_P4_RES_HELP trips, in registers for the whole
+// launch (lr_resident_groups, lr_scan.h) and the scans run those trips without load, wait and decode; the same groups per
+// lane in the same order through the same operations, so the sums are the doubles of NR = 0, which runs
+// lr_persist_scan_pair's loop for every trip.  The launch picks between 0 and LR_P4_NR (lr_p4_resident_choice).
+#ifndef LR_P4_NR
+#define LR_P4_NR 8            /* resident trips per scanner lane; 0: the resident form is not built */
+#endif
+#ifndef LR_P4_RES_HDR
+#define LR_P4_RES_HDR 0       /* 1: the header kept decoded (three registers per trip), 0: as its word (one) */
+#endif
+#ifndef LR_P4_NR_DRAW
+#define LR_P4_NR_DRAW 4       /* ... per lane of the two scanner waves that also make the draws ahead (waves 4, 5) */
+#endif
+#define LR_P4_RES_HELP 5      /* resident trips per helper lane: every trip lr_set_shares' rule gives the helpers */
 template <int H, bool GENERAL, bool PARAM /* a parametric sampler's chain step (DDRate, trend_rate) instead of the RJ sampler's */,
-          bool HELP = false, int CFG = LR_P4_CFG_GENERIC>
+          bool HELP = false, int CFG = LR_P4_CFG_GENERIC, int NR = 0>
 __global__ __launch_bounds__(LR_P4_THREADS, LR_P4_THREADS / 256) void lr_persist4_kernel(const lr_step_args* __restrict__ ap /* in global memory: a by-value argument struct measured
                                                                        0.2 us per launch faster, but one instantiation then kept a copy of it in scratch
                                                                        memory and read its fields from there in every phase */,
@@ -514,6 +535,7 @@ __global__ __launch_bounds__(LR_P4_THREADS, LR_P4_THREADS / 256) void lr_persist
                                                                        lr_p4_shares sh, long long n_iters, char* carry_all) {
     static_assert(!HELP || (!GENERAL && !PARAM), "helper waves: RJ sampler at unit resolution");
     static_assert(CFG == LR_P4_CFG_GENERIC || (HELP && H <= 264), "a configuration word comes with the helper waves");
+    static_assert(NR == 0 || HELP, "resident groups come with the helper waves");
     const lr_step_args& a = *ap;
     LR_PSTAMP(0);      // entry (LR_DIAG: wall-clock stamps of a launch's stages, blocks < 64; scratch/diag_p4_launch.py)
     constexpr int NW = LR_P4_THREADS / LR_WAVE;          // 16 waves: 2 steppers + 14 scanners (HELP: 2 + 2 helpers + 12)
@@ -609,7 +631,7 @@ __global__ __launch_bounds__(LR_P4_THREADS, LR_P4_THREADS / 256) void lr_persist
     constexpr int NA = NS + (HELP ? 2 : 0);
     auto leave_sums = [&](int pr, double s0, double s1) {
         if (LAST_SUMS) {
-            lr_p4_leave_sums<NA>(part, &arrived, &red[pr][2][0], wave >= W0 ? wave - W0 : NS + wave - 2, lane, scans_done, s0, s1);
+            lr_p4_leave_sums<NA, (NR > 0 ? NA / 2 : NA)>(part, &arrived, &red[pr][2][0], wave >= W0 ? wave - W0 : NS + wave - 2, lane, scans_done, s0, s1);
         } else {
             // (general times: every scanning wave adds its own lanes up; the stepper adds the waves' sums in wave order)
             s0 = lr_wave_sum(s0), s1 = lr_wave_sum(s1);
@@ -666,11 +688,31 @@ __global__ __launch_bounds__(LR_P4_THREADS, LR_P4_THREADS / 256) void lr_persist
     // (the pair is a compile-time constant at every call, as it is in the scanners' unrolled loop: the table's LDS address
     // then sits in the offset field of the slice's gathers - indexed by a run-time phase, each of the eight gathers of a
     // trip took a vector add with the table base first)
-    auto help_scan = [&](auto pr_) {
+    // NR > 0: the resident groups of a scanner lane and of a helper lane (equal shares: the helper form has no others),
+    // loaded once per launch BEHIND the prologue, whose scan goes through the loop: they are live in the iterations' loop of
+    // their role alone, not beside the prologue's draw duty
+    constexpr bool HDR = LR_P4_RES_HDR != 0;
+    lr_resident_groups<(NR > 0 ? NR : 1), HDR> res;
+    lr_resident_groups<LR_P4_RES_HELP, HDR> hres;
+    constexpr int NRD = NR > 0 ? LR_P4_NR_DRAW : 0;
+    lr_resident_groups<(NRD > 0 ? NRD : 1), HDR> dres;
+    // (the two scanner waves with the draw duty - Philox, exp, lr_log live beside the groups - keep NRD trips, in `dres`)
+    const bool res_scanner = NR > 0 && scanner && !(draw_ahead && wave - W0 < 2);
+    auto help_scan = [&](auto pr_, auto resident_) {
         constexpr int pr = decltype(pr_)::value;
         double s0 = 0.0, s1 = 0.0;
-        if (nh > 0) lr_persist_scan<H, GENERAL, 1, false, false>(reinterpret_cast<const char*>(tab[pr]), pk, 0, nh, tid - 2 * LR_WAVE, 2 * LR_WAVE, &s0, &s1);
+        if (decltype(resident_)::value) {
+            // (trips behind the resident ones - LR_P4_HELP_TRIPS above LR_P4_RES_HELP - as before)
+            const long long done = (long long)hres.trips * (2 * LR_WAVE);
+            lr_resident_trips(reinterpret_cast<const char*>(tab[pr]), hres, s0, s1);
+            if (nh > done) lr_persist_scan<H, GENERAL, 1, false, false>(reinterpret_cast<const char*>(tab[pr]), pk, done, nh - done, tid - 2 * LR_WAVE, 2 * LR_WAVE, &s0, &s1);
+        } else if (nh > 0) lr_persist_scan<H, GENERAL, 1, false, false>(reinterpret_cast<const char*>(tab[pr]), pk, 0, nh, tid - 2 * LR_WAVE, 2 * LR_WAVE, &s0, &s1);
         leave_sums(pr, s0, s1);
+    };
+    // NR > 0: a scanner wave's share of the scan for pair `pr` (a compile-time constant here too)
+    auto scan_resident = [&](auto pr_, double* s0, double* s1, lr_scan_tail* tail) {
+        constexpr int pr = decltype(pr_)::value;
+        lr_persist_scan_pair_resident(reinterpret_cast<const char*>(tab[pr]), pk.idx8 + nh, n8w, sid, LR_P4_SCANNERS, res, s0, s1, tail);
     };
     // prologue: pair 0's pending proposal is scanned so that phase A can step it - unless the launch before this one has
     // left the sums of that very scan (its last phase scored pair 0; lr_prepare_constants clears the flag whenever the
@@ -690,19 +732,20 @@ __global__ __launch_bounds__(LR_P4_THREADS, LR_P4_THREADS / 256) void lr_persist
         lr_scan_drain(tail);
         prologue_draws();
     }
-    if (helper && !carried) help_scan(std::integral_constant<int, 0>());
+    if (helper && !carried) help_scan(std::integral_constant<int, 0>(), std::false_type());
     __syncthreads();
     LR_PSTAMP(3);      // prologue done: pair 0's sums (scanned or carried), the first draws
     // phase ph of an iteration: the steppers advance pair `ph`, the scanners score pair `1 - ph`
     if (helper) {
+        if (NR > 0) lr_resident_load(hres, pk.idx8, nh, tid - 2 * LR_WAVE, 2 * LR_WAVE);
         for (long long iter = 0; iter < n_iters; ++iter) {
 #pragma unroll 1
             for (int ph = 0; ph < 2; ++ph) {
 #ifdef LR_DIAG
                 const unsigned long long dq0 = wall_clock64();
 #endif
-                if (ph == 0) help_scan(std::integral_constant<int, 1>());
-                else help_scan(std::integral_constant<int, 0>());
+                if (ph == 0) help_scan(std::integral_constant<int, 1>(), std::integral_constant<bool, (NR > 0)>());
+                else help_scan(std::integral_constant<int, 0>(), std::integral_constant<bool, (NR > 0)>());
                 help_duty(ph, (int)((2 * iter + ph + 1) & 0x3fffffff));
 #ifdef LR_DIAG
                 const unsigned long long dq1 = wall_clock64();
@@ -717,12 +760,45 @@ __global__ __launch_bounds__(LR_P4_THREADS, LR_P4_THREADS / 256) void lr_persist
             }
         }
     } else if (!scanner)
-        lr_persist4_steppers<(H <= 264 ? lr_bins_per_lane(H) : 0), ES, NW, PARAM ? 1 : 0, HELP, CFG>(
+        lr_persist4_steppers<(H <= 264 ? lr_bins_per_lane(H) : 0), ES, NW, PARAM ? 1 : 0, HELP, CFG, NR>(
             (const __attribute__((address_space(3))) lr_step_args*)&a_lds, c0, C, wave, lane,
             (__attribute__((address_space(3))) lr_seg_scratch*)&scratch[wave], (lr_lds_f64*)&st_f64[0][0], (lr_lds_i32*)&st_i32[0][0],
             (lr_lds_f64*)&red[0][0][0], (lr_lds_f64*)reinterpret_cast<double*>(tab[0]), 2 * LR_UNIT_PLANES * H,
             (lr_lds_f64*)&br_lds[0][0], n_iters, &draws[0], &hands[0]);
-    else
+    else if (res_scanner) {
+        // the ten scanner waves without a draw duty: the loop below without it, so that their NR trips of registers are
+        // not live beside its code
+        if constexpr (NR > 0) {
+        lr_resident_load(res, pk.idx8 + nh, n8w, sid, LR_P4_SCANNERS);
+        for (long long iter = 0; iter < n_iters; ++iter) {
+#pragma unroll
+            for (int ph = 0; ph < 2; ++ph) {
+#ifdef LR_DIAG
+                const unsigned long long dq0 = wall_clock64();
+#endif
+                {
+                    double s0 = 0.0, s1 = 0.0;
+                    lr_scan_tail tail;
+                    if (ph == 0) scan_resident(std::integral_constant<int, 1>(), &s0, &s1, &tail);
+                    else scan_resident(std::integral_constant<int, 0>(), &s0, &s1, &tail);
+                    leave_sums(1 - ph, s0, s1);
+                    lr_scan_drain(tail);
+                }
+#ifdef LR_DIAG
+                const unsigned long long dq1 = wall_clock64();
+#endif
+                __syncthreads();
+#ifdef LR_DIAG
+                if (lane == 0 && blockIdx.x < 64) {
+                    atomicAdd(&lr_diag_step[16384 + (blockIdx.x * 16 + wave) * 4 + 0], dq1 - dq0);
+                    atomicAdd(&lr_diag_step[16384 + (blockIdx.x * 16 + wave) * 4 + 1], wall_clock64() - dq1);
+                }
+#endif
+            }
+        }
+        }
+    } else {
+    if constexpr (NRD > 0) lr_resident_load(dres, pk.idx8 + nh, n8w, sid, LR_P4_SCANNERS);
     for (long long iter = 0; iter < n_iters; ++iter) {
 #pragma unroll
         for (int ph = 0; ph < 2; ++ph) {
@@ -732,6 +808,10 @@ __global__ __launch_bounds__(LR_P4_THREADS, LR_P4_THREADS / 256) void lr_persist
             {
                 double s0 = 0.0, s1 = 0.0;
                 lr_scan_tail tail;
+                if constexpr (NRD > 0) {
+                    if (ph == 0) lr_persist_scan_pair_resident(reinterpret_cast<const char*>(tab[1]), pk.idx8 + nh, n8w, sid, LR_P4_SCANNERS, dres, &s0, &s1, &tail);
+                    else lr_persist_scan_pair_resident(reinterpret_cast<const char*>(tab[0]), pk.idx8 + nh, n8w, sid, LR_P4_SCANNERS, dres, &s0, &s1, &tail);
+                } else
                 lr_persist_scan<H, GENERAL, 1, false, true>(reinterpret_cast<const char*>(tab[1 - ph]), pk, nh, n8w, sid, LR_P4_SCANNERS, &s0, &s1, nullptr, &tail);
                 leave_sums(1 - ph, s0, s1);
                 lr_scan_drain(tail);      // the idle prefetch of the scan's last trip (lr_scan.h)
@@ -748,6 +828,7 @@ __global__ __launch_bounds__(LR_P4_THREADS, LR_P4_THREADS / 256) void lr_persist
             }
 #endif
         }
+    }
     }
     LR_PSTAMP(4);      // the launch's iterations done
     if (wave < 4 && c0 + wave < C) {
@@ -1326,6 +1407,7 @@ extern "C" int lr_mcmc_create(const lr_mcmc_config* cfg, const double* ts, const
     e->p4.n_slots = 8;
     e->p4_help = lr_p4_help_choice(e);                  // (lr_mcmc_describe before init; latched again by lr_set_shares)
     e->p4_cfg = lr_p4_cfg_choice(e);
+    e->p4_resident = lr_p4_resident_choice(e);
     e->streaming = false;
     e->packed_scan = lay.packed_scan != 0;
     e->fork = nullptr;
@@ -1684,6 +1766,12 @@ extern "C" int lr_mcmc_steps(lr_engine* e, int64_t n_iters, void* stream_) {
         if (general && param) hipLaunchKernelGGL((lr_persist4_kernel<HH, true, true>), g4, b4, 0, stream, ap, pk, e->n8, e->p4, (long long)n, p4_carry);   \
         else if (general) hipLaunchKernelGGL((lr_persist4_kernel<HH, true, false>), g4, b4, 0, stream, ap, pk, e->n8, e->p4, (long long)n, p4_carry);      \
         else if (param) hipLaunchKernelGGL((lr_persist4_kernel<HH, false, true>), g4, b4, 0, stream, ap, pk, e->n8, e->p4, (long long)n, p4_carry);        \
+        else if (LR_P4_NR > 0 && e->p4_help && e->p4_resident && e->p4_cfg == LR_P4_CFG_BDI)   /* (resident groups: lr_p4_resident_choice) */ \
+            hipLaunchKernelGGL((lr_persist4_kernel<(HH <= 264 ? HH : 264), false, false, true, LR_P4_CFG_BDI, LR_P4_NR>), g4, b4, 0, stream, ap, pk, e->n8, e->p4, (long long)n, p4_carry); \
+        else if (LR_P4_NR > 0 && e->p4_help && e->p4_resident && e->p4_cfg == LR_P4_CFG_KEIDING)                                              \
+            hipLaunchKernelGGL((lr_persist4_kernel<(HH <= 264 ? HH : 264), false, false, true, LR_P4_CFG_KEIDING, LR_P4_NR>), g4, b4, 0, stream, ap, pk, e->n8, e->p4, (long long)n, p4_carry); \
+        else if (LR_P4_NR > 0 && e->p4_help && e->p4_resident)                                                                                \
+            hipLaunchKernelGGL((lr_persist4_kernel<(HH <= 264 ? HH : 264), false, false, true, LR_P4_CFG_GENERIC, LR_P4_NR>), g4, b4, 0, stream, ap, pk, e->n8, e->p4, (long long)n, p4_carry); \
         else if (e->p4_help && e->p4_cfg == LR_P4_CFG_BDI)      /* (helper waves: H <= 264, lr_p4_help_choice; the word: lr_p4_cfg_choice) */ \
             hipLaunchKernelGGL((lr_persist4_kernel<(HH <= 264 ? HH : 264), false, false, true, LR_P4_CFG_BDI>), g4, b4, 0, stream, ap, pk, e->n8, e->p4, (long long)n, p4_carry); \
         else if (e->p4_help && e->p4_cfg == LR_P4_CFG_KEIDING)                                                                \
@@ -1780,6 +1868,22 @@ extern "C" int lr_mcmc_warnings(lr_engine* e, int32_t* warnings, void* stream_) 
 extern "C" int lr_mcmc_p4_config(const lr_engine* e, int32_t* word) {
     if (!e || !word) return LR_ERR_NULL;
     *word = (e->persistent && e->lay.persistent == 2 && e->p4_help) ? e->p4_cfg : LR_P4_CFG_GENERIC;
+    return LR_OK;
+}
+
+// the four-chain kernel's resident scan groups in use (lr_resident_groups; all zero trips under LR_P4_RESIDENT=0 and for
+// every other kernel): out = resident trips per scanner lane (waves 6..15; waves 4, 5 keep at most LR_P4_NR_DRAW), per helper
+// lane, packed groups, the helpers' trips
+extern "C" int lr_mcmc_p4_resident(const lr_engine* e, int32_t* out) {
+    if (!e || !out) return LR_ERR_NULL;
+    const bool help = e->persistent && e->lay.persistent == 2 && e->p4_help;
+    const long long h = help ? e->p4.help_trips : 0;
+    const long long k_tot = (e->n8 - h * 128 + 767) / 768;        // trips of the first scanner wave: the most any wave makes
+    const bool on = help && e->p4_resident && LR_P4_NR > 0;
+    out[0] = on ? (int32_t)(k_tot < LR_P4_NR ? k_tot : LR_P4_NR) : 0;
+    out[1] = on ? (int32_t)(h < LR_P4_RES_HELP ? h : LR_P4_RES_HELP) : 0;
+    out[2] = (int32_t)e->n8;
+    out[3] = (int32_t)h;
     return LR_OK;
 }
 

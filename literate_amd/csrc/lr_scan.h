@@ -765,6 +765,127 @@ __device__ __forceinline__ void lr_persist_scan_pair(const char* __restrict__ lb
     *acc0_ = acc0, *acc1_ = acc1;
 }
 
+// RESIDENT groups.  A lane of a persistent kernel scores the same groups in every scan of a launch - group sid + k n_scan
+// on trip k - and the packed lineages never change during an engine's life: what the decode of a group yields (nine
+// full-rate instructions and a conversion per trip, a quarter of a trip's issue cycles) is a constant of the launch.  The
+// lane keeps the decoded groups of its first NR trips in registers - the seven slot byte offsets, which are relative to
+// the table and so serve both pairs, and the header either decoded (HDR: the birth entry's offset and the count as a
+// double, three registers) or as its word (one register; two masks and the conversion stay in the trip) - and every scan
+// runs those trips as straight-line code without a load, a wait or a decode: eight gathers, the same fixed tree,
+// fma(cnt, S, u), acc +=.  `trips` is the number of resident trips the WAVE runs: trip k only if the loop of
+// lr_persist_scan_pair would have run trip k for this wave (a scalar test per trip, as there: a lane past the end inside a
+// trip its wave runs scores a zero group, and no wave ever adds a trip of zeros the loop would not have added).
+template <int NR, bool HDR>
+struct lr_resident_groups {
+    unsigned int o[NR][LR_SLOTS];
+    unsigned int hd[NR];        // HDR: byte offset of the birth entry; otherwise the header word
+    double cnt[NR];             // HDR only
+    int trips;                  // wave-uniform, <= NR
+};
+
+// Once per launch: the groups of this lane's first min(NR, the wave's trips) trips over `n8` groups at `idx8`, by plain
+// loads (all issued before the first is decoded).  `sid` of a wave's first lane is a multiple of the wave size.
+template <int NR, bool HDR>
+__device__ __forceinline__ void lr_resident_load(lr_resident_groups<NR, HDR>& r, const uint4* __restrict__ idx8, long long n8,
+                                                 int sid, int n_scan) {
+    const int n = __builtin_amdgcn_readfirstlane((int)n8);
+    const int i0 = __builtin_amdgcn_readfirstlane(sid);
+    const int mine = i0 < n ? (n - i0 + n_scan - 1) / n_scan : 0;       // trips of this wave: those k with i0 + k n_scan < n
+    r.trips = __builtin_amdgcn_readfirstlane(mine < NR ? mine : NR);
+    uint4 w[NR];
+#pragma unroll
+    for (int k = 0; k < NR; ++k) {
+        w[k] = make_uint4(0u, 0u, 0u, 0u);
+        // (a lane past the end reads the zero-filled spare behind the groups: lr_groups_alloc keeps more than any stride)
+        if (k < r.trips) w[k] = idx8[sid + k * n_scan];
+    }
+#pragma unroll
+    for (int k = 0; k < NR; ++k) {
+        r.hd[k] = HDR ? (w[k].x & 0xfff0u) : w[k].x;
+        r.cnt[k] = (double)(w[k].x & 0xfu);
+        r.o[k][0] = lr_word_off16(w[k].x, 1), r.o[k][1] = lr_word_off16(w[k].y, 0), r.o[k][2] = lr_word_off16(w[k].y, 1);
+        r.o[k][3] = lr_word_off16(w[k].z, 0), r.o[k][4] = lr_word_off16(w[k].z, 1), r.o[k][5] = lr_word_off16(w[k].w, 0);
+        r.o[k][6] = lr_word_off16(w[k].w, 1);
+        // the decoded values are what stays: behind this the compiler cannot derive them from the word again
+#pragma unroll
+        for (int s = 0; s < LR_SLOTS; ++s) asm volatile("" : "+v"(r.o[k][s]));
+        asm volatile("" : "+v"(r.hd[k]));
+        if (HDR) asm volatile("" : "+v"(r.cnt[k]));
+    }
+}
+
+// the resident trips of one scan against the pair table at `lbase`: per trip the operations of lr_persist_scan_pair's loop
+// body on the same values, in trip order
+template <int NR, bool HDR>
+__device__ __forceinline__ void lr_resident_trips(const char* __restrict__ lbase, const lr_resident_groups<NR, HDR>& r,
+                                                  double& acc0, double& acc1) {
+#pragma unroll
+    for (int k = 0; k < NR; ++k) {
+        if (k >= r.trips) break;
+        // (!HDR: the two masks as asm statements - written in C++ the decoded header is hoisted out of the scans into
+        // three registers of its own after all)
+        unsigned int oS = r.hd[k], c4 = 0u;
+        if (!HDR) {
+            asm volatile("v_and_b32_e32 %0, 0xfff0, %1" : "=v"(oS) : "v"(r.hd[k]));
+            asm volatile("v_and_b32_e32 %0, 15, %1" : "=v"(c4) : "v"(r.hd[k]));
+        }
+        const double cnt = HDR ? r.cnt[k] : (double)c4;
+        const double2 S = *reinterpret_cast<const double2*>(lbase + oS);
+        const double2 E0 = *reinterpret_cast<const double2*>(lbase + r.o[k][0]), E1 = *reinterpret_cast<const double2*>(lbase + r.o[k][1]);
+        const double2 E2 = *reinterpret_cast<const double2*>(lbase + r.o[k][2]), E3 = *reinterpret_cast<const double2*>(lbase + r.o[k][3]);
+        const double2 E4 = *reinterpret_cast<const double2*>(lbase + r.o[k][4]), E5 = *reinterpret_cast<const double2*>(lbase + r.o[k][5]);
+        const double2 E6 = *reinterpret_cast<const double2*>(lbase + r.o[k][6]);
+        // fixed pairwise tree over the slots, then the birth entry `count` times
+        const double u0 = ((E0.x + E1.x) + (E2.x + E3.x)) + ((E4.x + E5.x) + E6.x);
+        const double u1 = ((E0.y + E1.y) + (E2.y + E3.y)) + ((E4.y + E5.y) + E6.y);
+        acc0 += fma(cnt, S.x, u0);
+        acc1 += fma(cnt, S.y, u1);
+    }
+}
+
+// lr_persist_scan_pair<H, 1, true> (hand-placed loads, the wave's own trip count) with the first r.trips trips resident:
+// the loop starts at trip r.trips - its first group is requested before the resident trips and has landed behind them -
+// and runs no trip at all for a wave whose trips are all resident (r.trips < NR: the wave has no more).
+template <int NR, bool HDR>
+__device__ __forceinline__ void lr_persist_scan_pair_resident(const char* __restrict__ lbase, const uint4* __restrict__ idx8,
+                                                              long long n8, long long sid, int n_scan,
+                                                              const lr_resident_groups<NR, HDR>& r, double* acc0_,
+                                                              double* acc1_, lr_scan_tail* tail) {
+    double acc0 = *acc0_, acc1 = *acc1_;
+    const int n = __builtin_amdgcn_readfirstlane((int)n8);
+    const unsigned int stride_b = (unsigned int)n_scan * 16u;
+    const char* gbase = lr_uniform_ptr(idx8) + (size_t)((unsigned int)r.trips * stride_b);
+    const unsigned int off = (unsigned int)sid * 16u;
+    int i0 = __builtin_amdgcn_readfirstlane((int)sid) + r.trips * n_scan;
+    bool has = i0 < n;
+    lr_u32x4 w = {0u, 0u, 0u, 0u};
+    // (unconditionally, as every load of the loop: a wave without a trip left requests a group - or zeros of the spare -
+    // that it will not score)
+    lr_gload16_async(w, gbase, off);
+    lr_resident_trips(lbase, r, acc0, acc1);
+    while (has) {
+        lr_gload_wait<0>(w);
+        const unsigned int oS = w.x & 0xfff0u;
+        const double cnt = (double)(w.x & 0xfu);
+        const unsigned int o0 = lr_word_off16(w.x, 1), o1 = lr_word_off16(w.y, 0), o2 = lr_word_off16(w.y, 1),
+                           o3 = lr_word_off16(w.z, 0), o4 = lr_word_off16(w.z, 1), o5 = lr_word_off16(w.w, 0),
+                           o6 = lr_word_off16(w.w, 1);
+        i0 += n_scan, has = i0 < n, gbase += has ? stride_b : 0u;
+        lr_gload16_async(w, gbase, off);
+        const double2 S = *reinterpret_cast<const double2*>(lbase + oS);
+        const double2 E0 = *reinterpret_cast<const double2*>(lbase + o0), E1 = *reinterpret_cast<const double2*>(lbase + o1);
+        const double2 E2 = *reinterpret_cast<const double2*>(lbase + o2), E3 = *reinterpret_cast<const double2*>(lbase + o3);
+        const double2 E4 = *reinterpret_cast<const double2*>(lbase + o4), E5 = *reinterpret_cast<const double2*>(lbase + o5);
+        const double2 E6 = *reinterpret_cast<const double2*>(lbase + o6);
+        const double u0 = ((E0.x + E1.x) + (E2.x + E3.x)) + ((E4.x + E5.x) + E6.x);
+        const double u1 = ((E0.y + E1.y) + (E2.y + E3.y)) + ((E4.y + E5.y) + E6.y);
+        acc0 += fma(cnt, S.x, u0);
+        acc1 += fma(cnt, S.y, u1);
+    }
+    tail->w = w, tail->f0 = lr_u32x4{0u, 0u, 0u, 0u};
+    *acc0_ = acc0, *acc1_ = acc1;
+}
+
 // The pair-sum planes of a pair table from its E plane.  `tab` = the table's doubles (entry e of chain c at 2 e + c);
 // plane 2 + d, entry j = E[j] + E[j + d] for the death entries j, j + d <= n_bins + 1 that lineages can be paired on (the
 // extant block of model 3 behind them is gathered through single slots only).

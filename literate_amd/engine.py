@@ -264,6 +264,13 @@ class ChainEngine:
         _hip.check(self.lib.lr_mcmc_p4_config(self.handle, C.byref(w)), "lr_mcmc_p4_config")
         return int(w.value)
 
+    def p4_resident(self):
+        """Resident scan groups of the four-chain kernel steps() runs: (resident trips per scanner lane, per helper lane,
+        packed groups, the helper lanes' trips); no resident trips for another kernel or with LR_P4_RESIDENT=0 at init()."""
+        out = (C.c_int32 * 4)()
+        _hip.check(self.lib.lr_mcmc_p4_resident(self.handle, out), "lr_mcmc_p4_resident")
+        return tuple(int(v) for v in out)
+
     def timed_steps(self, n):
         """steps(n) bracketed by HIP events on the launch stream; returns elapsed device ms (blocks)."""
         ms = C.c_float(0.0)
