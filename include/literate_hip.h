@@ -97,7 +97,10 @@ int lr_expand_rates(const double* rates, const double* times, const int32_t* K, 
  * Few states on few lineages (n <= 2^18, C <= 64, n * C <= 2^21: the reference's own use, one state per iteration) take
  * ONE launch - a block per state builds its table in LDS and walks all lineages (LR_LOGLIK_SMALL=0: never); lam_bins,
  * mu_bins and out_loglik may then as well be pinned HOST memory (device-accessible), which saves the caller two copies
- * and the synchronisation (literate_amd/ops.py LoglikSession).                                  */
+ * and the synchronisation (literate_amd/ops.py LoglikSession).
+ * n_bins: 1 .. LR_MAX_BINS for models 0 - 2.  Model 3 keeps two table classes per chain (dead and extant lineages), 64
+ * bytes per table entry of n_bins + 2, and one chain's tables must fit the scan's 150 KiB of LDS: n_bins <= 2398.  Above
+ * its cap the call and the size query return LR_ERR_SIZE.                                        */
 int64_t lr_bd_loglik_workspace_bytes(int64_t n, int32_t n_bins, int32_t n_chains, int32_t model);
 /* measurement hook: the launch shape lr_bd_loglik_batch uses for these sizes - out[0] = Cb, the chains one pass over
  * ts / te scores (the call makes ceil(n_chains / Cb) passes = 16 B x n x passes of algorithmic HBM reads), out[1] =

@@ -21,17 +21,20 @@ def bin_terms(lam, mu, model, br_length, dtype):
     m = 2 if model == 3 else model
     if dtype == np.float64:
         logB, logD, R, const = lo.per_lineage_tables(lam, mu, m, br_length)
-        assert const == 0.0
+        assert const == 0.0 or m == 1      # (model 1's constant belongs to no lineage: tests/helpers/loglik_ref.py adds it)
         return logB, logD, R
     lam, mu = np.asarray(lam, dtype=dtype), np.asarray(mu, dtype=dtype)
     with np.errstate(divide="ignore", invalid="ignore"):
         if m >= 2:
             return np.log(lam), np.log(mu), lam + mu
-        assert m == 0
+        assert m in (0, 1)
         k = np.asarray(br_length, dtype=dtype)
         ok = k > 0
         logB, logD, R = np.zeros_like(lam), np.zeros_like(lam), np.zeros_like(lam)
-        logB[ok], logD[ok], R[ok] = np.log(k[ok] * lam[ok]), np.log(mu[ok] * k[ok]), lam[ok] + mu[ok]
+        if m == 0:
+            logB[ok], logD[ok], R[ok] = np.log(k[ok] * lam[ok]), np.log(mu[ok] * k[ok]), lam[ok] + mu[ok]
+        else:
+            logB[ok], logD[ok], R[ok] = np.log(lam[ok]), np.log(mu[ok] * k[ok]), mu[ok]
         return logB, logD, R
 
 

@@ -421,6 +421,8 @@ def test_loglik_bad_arguments(ops):
         ops.bd_loglik_batch(ts, te, 0.0, lam, lam, 7, None)
     with pytest.raises(ValueError, match="LR_ERR_SIZE"):
         ops.bd_loglik_batch(ts, te, 0.0, np.full((1, 5000), .1), np.full((1, 5000), .1), 2)
+    with pytest.raises(ValueError, match="LR_ERR_SIZE"):        # model 3's own cap (two table classes): 2398 bins
+        ops.bd_loglik_batch(ts, te, 0.0, np.full((1, 2399), .1), np.full((1, 2399), .1), 3)
 
 
 def test_streaming_kernels_at_1e8_lineages(ops):
