@@ -1,4 +1,5 @@
-"""ctypes binding of libliterate_hip.so (include/literate_hip.h, include/literate_hip_age.h, include/literate_hip_ade.h).  Fails loudly: no fallback."""
+"""ctypes binding of libliterate_hip.so (include/literate_hip.h, include/literate_hip_age.h, include/literate_hip_ade.h,
+include/literate_hip_adej.h).  Fails loudly: no fallback."""
 import ctypes as C
 import os
 
@@ -12,6 +13,7 @@ ERRORS = {-1: "LR_ERR_NULL", -2: "LR_ERR_SIZE", -3: "LR_ERR_MODEL", -4: "LR_ERR_
 
 LR_KMAX, LR_ROW, LR_MAX_BINS = 32, 64, 4094
 LR_ADE_MAX_BINS = 512      # lr_ade_classes, lr_ade_profile (include/literate_hip_ade.h)
+LR_ADEJ_MAX_BINS, LR_ADEJ_MOVES, LR_ADEJ_STATE_W, LR_ADEJ_ROW_W = 128, 5, 96, 73      # include/literate_hip_adej.h
 LR_WARN_KCAP = 2
 LR_STATE_ROWS, LR_ISTATE_ROWS = 9, 5
 LR_TRACE_HEAD = 13
@@ -47,7 +49,8 @@ class McmcLayout(C.Structure):
                 ("spec_chains_per_team", c_i32), ("streaming", c_i32), ("packed_scan", c_i32), ("reserved3", c_i32)]
 
 
-# name -> (restype, argtypes); exactly the symbols include/literate_hip.h, literate_hip_age.h and literate_hip_ade.h declare (+ the RNG debug hook)
+# name -> (restype, argtypes); exactly the symbols include/literate_hip.h, literate_hip_age.h, literate_hip_ade.h and
+# literate_hip_adej.h declare (+ the RNG debug hook)
 SIGNATURES = {
     "lr_version": (c_i32, []),
     "lr_bin_events_workspace_bytes": (c_i64, [c_i64, c_i32]),
@@ -94,6 +97,12 @@ SIGNATURES = {
     "lr_ade_classes": (c_i32, [c_vp, c_vp, c_i64, c_f64, c_i32, c_vp, c_vp, c_vp, c_vp]),
     "lr_ade_profile_workspace_bytes": (c_i64, [c_i32, c_i32, c_i32]),
     "lr_ade_profile": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "lr_adej_workspace_bytes": (c_i64, [c_i32]),
+    "lr_adej_prepare": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_i64, c_vp]),
+    "lr_adej_loglik": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp]),
+    "lr_adej_init": (c_i32, [c_vp, c_i64, c_i32, c_f64, c_i32, c_i32, c_f64, c_f64, C.c_uint64, c_i32, c_i32, c_vp, c_vp]),
+    "lr_adej_steps": (c_i32, [c_vp, c_i64, c_i32, c_f64, c_i32, c_i32, c_f64, c_f64, C.c_uint64, c_i32, c_i32, c_vp, c_i64, c_i64,
+                              c_i32, c_vp, c_i64, c_vp]),
     "lr_ess_summary_workspace_bytes": (c_i64, [c_i32, c_i32, c_i32, c_vp, c_i32, c_f64, c_i32]),
     "lr_ess_summary": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_i32, c_f64, c_i32, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
     "lr_col_summary_workspace_bytes": (c_i64, [c_i32, c_i32, c_i32, c_vp, c_i32, c_f64, c_i32, c_i32]),

@@ -25,7 +25,7 @@ continuous times are coarsened to their bins (a birth to the start of its bin, a
 5. <stem>_ADE.tsv (one row) and <stem>_ADE_shape.tsv (one row per coarse and fine node).
 
 What this is not: the sampled rates were fitted under k = 1, so the result is an estimate CONDITIONAL on the run's time
-pattern, not a joint posterior of shape and rates; a joint sampler would be the next step.
+pattern, not a joint posterior of shape and rates; the joint sampler of both is literate_amd/ade_joint.py (--ade_joint).
 
 Refused where --ppc_age is refused (-model_BDI 3, -pyrate_output, -rm_first_bin 1), and with more than LR_ADE_MAX_BINS bins."""
 import math

@@ -143,7 +143,7 @@ __device__ __forceinline__ int lr_wave_exclusive_scan_i32(int x) {
 #define LR_P_ACCEPT 9
 #define LR_P_INIT 10
 // (purposes defined beside their users: 16-19 lr_dd.h, 24 lr_sim.hip / lr_simbatch.hip, 32-35 lr_dd.h, 40 lr_prior.hip,
-// 41 lr_age.hip)
+// 41 lr_age.hip, 48-51 lr_adej.hip)
 #define LR_GAMMA_MAX_ATTEMPTS 32
 
 struct lr_u2 {

@@ -816,6 +816,114 @@ def ade_profile(dead, cens, mu_bins, shapes, out=None):
     return ll, c, flag
 
 
+ADEJ_MOVES = ("mult", "shape", "add", "remove", "gibbs")
+ADEJ_ROW_HEAD = ("it", "posterior", "lik", "prior", "shape", "log_shape", "K", "mean_rate", "rate_hp", "poi_hp")
+ADEJ_STATE = {"K": 0, "log_shape": 1, "rate_hp": 2, "poi_hp": 3, "lik": 4, "prior": 5, "proposed": 6, "accepted": 11, "rates": 16,
+              "times": 48}
+AdejSettings = namedtuple("AdejSettings", "const use_rate_hp poisson_prior win", defaults=(0, 1, 0.0, 0.4))
+AdejSettings.__doc__ = """The joint sampler's switches (include/literate_hip_adej.h): const - one rate, no RJ moves; use_rate_hp - 0: the
+rates' Gamma prior keeps rate 1; poisson_prior - 0: hyper-prior on the Poisson rate of K, > 0: that fixed rate; win - width of
+the window of the log-shape move."""
+
+
+class AdejData:
+    """lr_adej_prepare's workspace (a uint8 device tensor of exactly the queried size) and its bin count"""
+
+    def __init__(self, ws, n_bins):
+        self.ws, self.n_bins, self.device = ws, int(n_bins), ws.device
+
+
+def adej_prepare(dead, cens, out=None):
+    """The data side of the joint sampler of (death-rate skyline, Weibull shape) (lr_adej_prepare,
+    include/literate_hip_adej.h): from ade_classes' dead [A, A] and cens [A] the numbers at risk and the class list ->
+    AdejData, A <= LR_ADEJ_MAX_BINS.  out: the AdejData of an earlier call of the same size to write into."""
+    torch = _torch()
+    lib = _hip.load()
+    dead = _dev(dead, torch.int64)
+    dev = dead.device
+    cens = _dev(cens, torch.int64, dev)
+    if dead.dim() != 2 or dead.shape[0] != dead.shape[1] or cens.numel() != dead.shape[0]:
+        raise ValueError("shape mismatch: dead [A, A]; cens [A]")
+    A = int(cens.numel())
+    nbytes = lib.lr_adej_workspace_bytes(A)
+    if nbytes < 0:
+        _hip.check(int(nbytes), "lr_adej_workspace_bytes")
+    if out is None:
+        ws = alloc_workspace(nbytes, dev)
+    else:
+        ws = out.ws
+        if out.n_bins != A or ws.numel() != nbytes or ws.device != dev:
+            raise ValueError("out must be the AdejData of a call of the same size")
+    rc = _hip.launch(lib.lr_adej_prepare, dev, _hip.ptr(dead), _hip.ptr(cens), A, _hip.ptr(ws), ws.numel())
+    _hip.check(rc, "lr_adej_prepare")
+    return AdejData(ws, A)
+
+
+def adej_loglik(data, mu_bins, shapes, out=None):
+    """l(mu, k) of the joint sampler's model for the S rows of mu_bins [S, A] and shapes [S] (lr_adej_loglik) -> (ll [S]
+    float64, flag [S] int32: bit 0 a bad rate, bit 1 a bad shape; a flagged row is NaN); device tensors."""
+    torch = _torch()
+    lib = _hip.load()
+    dev = data.device
+    mu = _dev(mu_bins, torch.float64, dev)
+    sh = _dev(shapes, torch.float64, dev).reshape(-1)
+    if mu.dim() != 2 or mu.shape[1] != data.n_bins or sh.numel() != mu.shape[0]:
+        raise ValueError("shape mismatch: mu_bins [S, A]; shapes [S]")
+    S = int(mu.shape[0])
+    ll, flag = _ade_out(out, ((S,), (S,)), (torch.float64, torch.int32), dev, "(ll, flag)")
+    rc = _hip.launch(lib.lr_adej_loglik, dev, _hip.ptr(data.ws), data.ws.numel(), data.n_bins, _hip.ptr(mu), _hip.ptr(sh), S,
+                     _hip.ptr(ll), _hip.ptr(flag))
+    _hip.check(rc, "lr_adej_loglik")
+    return ll, flag
+
+
+def _adej_args(data, t0, st, seed, chain0, n_chains):
+    return (_hip.ptr(data.ws), data.ws.numel(), data.n_bins, float(t0), int(st.const), int(st.use_rate_hp), float(st.poisson_prior),
+            float(st.win), int(seed) & 0xFFFFFFFFFFFFFFFF, int(chain0), int(n_chains))
+
+
+def adej_init(data, t0, n_chains, seed, settings=AdejSettings(), chain0=0, out=None):
+    """The initial state of chains chain0 .. chain0 + n_chains - 1 (lr_adej_init) -> state [n_chains, LR_ADEJ_STATE_W]
+    (slots: ADEJ_STATE)."""
+    torch = _torch()
+    lib = _hip.load()
+    (state,) = _ade_out(out, ((max(int(n_chains), 0), _hip.LR_ADEJ_STATE_W),), (torch.float64,), data.device, "(state,)")
+    rc = _hip.launch(lib.lr_adej_init, data.device, *_adej_args(data, t0, settings, seed, chain0, n_chains), _hip.ptr(state))
+    _hip.check(rc, "lr_adej_init")
+    return state
+
+
+def adej_rows_needed(it0, n_iters, s_freq):
+    s = int(s_freq)
+    return (int(it0) + int(n_iters) + s - 1) // s - (int(it0) + s - 1) // s
+
+
+def adej_steps(data, t0, state, it0, n_iters, s_freq, seed, settings=AdejSettings(), chain0=0, out=None):
+    """Iterations it0 .. it0 + n_iters - 1 of every chain of `state` (updated in place; lr_adej_steps) -> rows [n, C,
+    LR_ADEJ_ROW_W], one per chain and iteration with it % s_freq == 0 (columns: ADEJ_ROW_HEAD, then LR_KMAX rates and
+    LR_KMAX - 1 shift times, NaN where unused)."""
+    torch = _torch()
+    lib = _hip.load()
+    if state.dtype != torch.float64 or state.dim() != 2 or state.shape[1] != _hip.LR_ADEJ_STATE_W or not state.is_contiguous() \
+            or state.device != data.device:
+        raise ValueError("state must be adej_init's [chains, LR_ADEJ_STATE_W] float64 tensor on the data's device")
+    C = int(state.shape[0])
+    n = adej_rows_needed(it0, n_iters, s_freq) if int(s_freq) >= 1 and int(n_iters) >= 0 and int(it0) >= 0 else 0
+    (rows,) = _ade_out(out, ((max(n, 0), C, _hip.LR_ADEJ_ROW_W),), (torch.float64,), data.device, "(rows,)")
+    rc = _hip.launch(lib.lr_adej_steps, data.device, *_adej_args(data, t0, settings, seed, chain0, C), _hip.ptr(state), int(it0),
+                     int(n_iters), int(s_freq), _hip.ptr(rows) if rows.numel() else None, n)
+    _hip.check(rc, "lr_adej_steps")
+    return rows
+
+
+def adej_run(data, t0, n_chains, n_iter, s_freq, seed, settings=AdejSettings(), chain0=0):
+    """A whole run of the joint sampler: lr_adej_init, then n_iter iterations in one launch -> (rows [n_iter / s_freq
+    rounded up, n_chains, LR_ADEJ_ROW_W], state [n_chains, LR_ADEJ_STATE_W]); device tensors."""
+    state = adej_init(data, t0, n_chains, seed, settings, chain0)
+    rows = adej_steps(data, t0, state, 0, n_iter, s_freq, seed, settings, chain0)
+    return rows, state
+
+
 EssSummary = namedtuple("EssSummary", "mean ess act se_mean stop_lag pooled_mean pooled_ess rhat n")
 EssSummary.__doc__ = """lr_ess_summary's results.  mean, ess, act (in samples), se_mean float64 and stop_lag int32: [C, K] per chain and
 column; pooled_mean, pooled_ess, rhat: [K]; n: rows kept per chain.  ESS and ACT are NaN, SE 0 and the stop lag 0 where a

@@ -58,6 +58,14 @@ def build_parser():
                    'draws of the per-bin death rates (this burn-in fraction dropped per chain), beside the constant-baseline '
                    'Weibull of the reference ADE scripts; at most 512 time bins; not with -rm_first_bin 1 (extension)')
     p.add_argument('--ade_draws', type=int, default=1000, help='posterior draws the age-dependent extinction fit conditions on')
+    p.add_argument('--ade_joint', type=float, default=-1.0, help='after the run, write <stem>_ADE_joint.tsv, <stem>_ADE_joint_rates.tsv '
+                   'and <stem>_ADE_joint_draws.npz beside the logs: age-dependent extinction sampled jointly - a sampler of its own '
+                   'over (baseline death-rate skyline, Weibull shape) on the GPU, --chains chains on the run\'s lineages, window '
+                   'and seed, this burn-in fraction dropped per chain; what --ade\'s conditional fit becomes once the rate '
+                   'shifts may move with the shape; at most 128 time bins; refused where --ade is')
+    p.add_argument('--ade_joint_n', type=int, default=0, help='iterations of the joint sampler (default: -n)')
+    p.add_argument('--ade_joint_s', type=int, default=0, help='sampling frequency of the joint sampler (default: -s)')
+    p.add_argument('--ade_joint_win', type=float, default=0.4, help='width of the joint sampler\'s window move in log shape')
     p.add_argument('--waic', type=float, default=-1.0, help='after the run, write <stem>_WAIC.tsv and <stem>_WAIC_pointwise.npz beside the logs: WAIC (elpd, '
                    'p_waic and their standard errors) from --waic_draws posterior draws of the parameters, at the '
                    'per-bin rates the trend gives them (this burn-in fraction dropped per chain), the per-lineage '
@@ -101,6 +109,11 @@ def main(argv=None):
     if args.ade != -1.0:
         from literate_amd.ade import arg_error as ade_arg_error
         err = ade_arg_error(args.ade, args.ade_draws, rm_first_bin=args.rm_first_bin)
+        if err:
+            raise SystemExit(err)
+    if args.ade_joint != -1.0:
+        from literate_amd.ade_joint import arg_error as adej_arg_error
+        err = adej_arg_error(args.ade_joint, args.ade_joint_n or args.n, args.ade_joint_s or args.s, args.ade_joint_win, rm_first_bin=args.rm_first_bin)
         if err:
             raise SystemExit(err)
     if args.waic != -1.0:
@@ -194,6 +207,10 @@ def main(argv=None):
     if args.ade != -1.0 and n_samples:
         from literate_amd import ade
         ade.write_run(eng, n_local, args.chains, world, rank, args.ade, args.ade_draws, "%s_%s" % (stem, args.trend_index))
+    if args.ade_joint != -1.0:
+        from literate_amd import ade_joint
+        ade_joint.write_run(eng, args.chains, rank, args.ade_joint, args.ade_joint_n or args.n, args.ade_joint_s or args.s,
+                            args.ade_joint_win, seed, "%s_%s" % (stem, args.trend_index))
     if args.waic != -1.0 and n_samples:
         from literate_amd import waic
         waic.write_run(eng, n_local, args.chains, world, rank, args.waic, args.waic_draws, "%s_%s" % (stem, args.trend_index))
