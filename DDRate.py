@@ -63,6 +63,20 @@ def build_parser():
     p.add_argument('--ade_joint_n', type=int, default=0, help='iterations of the joint sampler (default: -n)')
     p.add_argument('--ade_joint_s', type=int, default=0, help='sampling frequency of the joint sampler (default: -s)')
     p.add_argument('--ade_joint_win', type=float, default=0.4, help='width of the joint sampler\'s window move in log shape')
+    p.add_argument('--mlik', type=float, default=-1.0, help='after the run, write <stem>_MLIK.tsv, <stem>_MLIK_temps.tsv and <stem>_MLIK.npz '
+                   'beside the logs: the marginal likelihood log Z of this -m_birth / -m_death model, by stepping stones (and '
+                   'thermodynamic integration) over --mlik_temps power posteriors x --mlik_reps replicates, chains of their own '
+                   'on the GPU on the run\'s per-bin statistics and seed, this burn-in fraction dropped per chain; it is the '
+                   'marginal likelihood under the prior as the sampler realises it (a parameter moved by the multiplier keeps '
+                   'its sign, the midpoint is uniform on its reflected range); rank models run on the same data with `python '
+                   '-m literate_amd.mlik A_MLIK.npz B_MLIK.npz` (2 ln BF); at most 512 time bins; one GPU (extension)')
+    p.add_argument('--mlik_temps', type=int, default=16, help='temperatures of the ladder, beta_j = (j / (T - 1)) ** (1 / alpha)')
+    p.add_argument('--mlik_reps', type=int, default=8, help='independent replicates of the ladder (the standard error is theirs)')
+    p.add_argument('--mlik_n', type=int, default=0, help='iterations of the power-posterior chains (default: -n)')
+    p.add_argument('--mlik_s', type=int, default=0, help='their sampling frequency (default: -s)')
+    p.add_argument('--mlik_alpha', type=float, default=0.3, help='exponent of the temperature ladder')
+    p.add_argument('--mlik_widen', type=float, default=8.0, help='cap of the window scale min(beta ** -1/2, widen) of the cold '
+                   'chains (1: the reference\'s windows at every temperature)')
     p.add_argument('--waic', type=float, default=-1.0, help='after the run, write <stem>_WAIC.tsv and <stem>_WAIC_pointwise.npz beside the logs: WAIC (elpd, '
                    'p_waic and their standard errors) from --waic_draws posterior draws of the parameters, at the '
                    'per-bin rates they give under the observed diversity (this burn-in fraction dropped per chain), the '
@@ -111,6 +125,12 @@ def main(argv=None):
     if args.ade_joint != -1.0:
         from literate_amd.ade_joint import arg_error as adej_arg_error
         err = adej_arg_error(args.ade_joint, args.ade_joint_n or args.n, args.ade_joint_s or args.s, args.ade_joint_win, rm_first_bin=args.rm_first_bin)
+        if err:
+            raise SystemExit(err)
+    if args.mlik != -1.0:
+        from literate_amd.mlik import arg_error as mlik_arg_error
+        err = mlik_arg_error(args.mlik, args.mlik_temps, args.mlik_reps, args.mlik_n or args.n, args.mlik_s or args.s, args.mlik_alpha,
+                             args.mlik_widen)
         if err:
             raise SystemExit(err)
     if args.waic != -1.0:
@@ -205,6 +225,10 @@ def main(argv=None):
         from literate_amd import ade_joint
         ade_joint.write_run(eng, args.chains, rank, args.ade_joint, args.ade_joint_n or args.n, args.ade_joint_s or args.s,
                             args.ade_joint_win, seed, stem)
+    if args.mlik != -1.0:
+        from literate_amd import mlik
+        mlik.write_run(eng, rank, args.mlik, args.mlik_temps, args.mlik_reps, args.mlik_n or args.n, args.mlik_s or args.s,
+                       args.mlik_alpha, args.mlik_widen, seed, stem, init_death=args.fix_death)
     if args.waic != -1.0 and n_samples:
         from literate_amd import waic
         waic.write_run(eng, n_local, args.chains, world, rank, args.waic, args.waic_draws, stem)

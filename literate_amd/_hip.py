@@ -1,5 +1,5 @@
 """ctypes binding of libliterate_hip.so (include/literate_hip.h, include/literate_hip_age.h, include/literate_hip_ade.h,
-include/literate_hip_adej.h).  Fails loudly: no fallback."""
+include/literate_hip_adej.h, include/literate_hip_mlik.h).  Fails loudly: no fallback."""
 import ctypes as C
 import os
 
@@ -14,6 +14,7 @@ ERRORS = {-1: "LR_ERR_NULL", -2: "LR_ERR_SIZE", -3: "LR_ERR_MODEL", -4: "LR_ERR_
 LR_KMAX, LR_ROW, LR_MAX_BINS = 32, 64, 4094
 LR_ADE_MAX_BINS = 512      # lr_ade_classes, lr_ade_profile (include/literate_hip_ade.h)
 LR_ADEJ_MAX_BINS, LR_ADEJ_MOVES, LR_ADEJ_STATE_W, LR_ADEJ_ROW_W = 128, 5, 96, 73      # include/literate_hip_adej.h
+LR_MLIK_MAX_BINS, LR_MLIK_MAX_TEMPS, LR_MLIK_MOVES, LR_MLIK_STATE_W, LR_MLIK_ROW_W = 512, 128, 2, 16, 12      # include/literate_hip_mlik.h
 LR_WARN_KCAP = 2
 LR_STATE_ROWS, LR_ISTATE_ROWS = 9, 5
 LR_TRACE_HEAD = 13
@@ -50,7 +51,7 @@ class McmcLayout(C.Structure):
 
 
 # name -> (restype, argtypes); exactly the symbols include/literate_hip.h, literate_hip_age.h, literate_hip_ade.h and
-# literate_hip_adej.h declare (+ the RNG debug hook)
+# literate_hip_adej.h, literate_hip_mlik.h declare (+ the RNG debug hook)
 SIGNATURES = {
     "lr_version": (c_i32, []),
     "lr_bin_events_workspace_bytes": (c_i64, [c_i64, c_i32]),
@@ -103,6 +104,11 @@ SIGNATURES = {
     "lr_adej_init": (c_i32, [c_vp, c_i64, c_i32, c_f64, c_i32, c_i32, c_f64, c_f64, C.c_uint64, c_i32, c_i32, c_vp, c_vp]),
     "lr_adej_steps": (c_i32, [c_vp, c_i64, c_i32, c_f64, c_i32, c_i32, c_f64, c_f64, C.c_uint64, c_i32, c_i32, c_vp, c_i64, c_i64,
                               c_i32, c_vp, c_i64, c_vp]),
+    "lr_mlik_init": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_f64, c_f64, c_i32, c_i32, c_f64, c_vp, c_vp, c_i32, C.c_uint64, c_i32, c_i32,
+                             c_vp, c_vp]),
+    "lr_mlik_steps": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_f64, c_f64, c_i32, c_i32, c_f64, c_vp, c_vp, c_i32, C.c_uint64, c_i32, c_i32,
+                              c_vp, c_i64, c_i64, c_i32, c_vp, c_i64, c_vp]),
+    "lr_mlik_estimate": (c_i32, [c_vp, c_i64, c_i32, c_i32, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "lr_ess_summary_workspace_bytes": (c_i64, [c_i32, c_i32, c_i32, c_vp, c_i32, c_f64, c_i32]),
     "lr_ess_summary": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_i32, c_f64, c_i32, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
     "lr_col_summary_workspace_bytes": (c_i64, [c_i32, c_i32, c_i32, c_vp, c_i32, c_f64, c_i32, c_i32]),

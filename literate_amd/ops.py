@@ -924,6 +924,102 @@ def adej_run(data, t0, n_chains, n_iter, s_freq, seed, settings=AdejSettings(), 
     return rows, state
 
 
+MLIK_ROW = ("it", "beta", "lik", "prior", "l_max", "k", "x0", "div_0", "L", "m_max", "nuB", "nuD")
+MLIK_STATE = {"args": 0, "lik": 8, "prior": 9, "proposed": 10, "accepted": 12, "beta": 14, "scale": 15}
+MlikEstimate = namedtuple("MlikEstimate", "stone ss lik_mean lik_var ti pooled")
+MlikEstimate.__doc__ = """lr_mlik_estimate's results (include/literate_hip_mlik.h).  stone [R, T - 1], ss [R], lik_mean, lik_var [R, T], ti [R],
+pooled [T] (the pooled stones and, last, their sum).  Device tensors."""
+
+
+class MlikData:
+    """The statistics the DDRate likelihood is a function of (create_bins' N_SPEC, N_EXTI, DT as float64 device tensors), the
+    window and the model: what every lr_mlik_* call of one run shares."""
+
+    def __init__(self, n_spec, n_exti, DT, origin, present, m_birth=2, m_death=2, init_death=0.1, device=None):
+        torch = _torch()
+        self.n_spec = _dev(n_spec, torch.float64, device).reshape(-1)
+        self.device = self.n_spec.device
+        self.n_exti = _dev(n_exti, torch.float64, self.device).reshape(-1)
+        self.DT = _dev(DT, torch.float64, self.device).reshape(-1)
+        if self.n_exti.numel() != self.n_spec.numel() or self.DT.numel() != self.n_spec.numel():
+            raise ValueError("shape mismatch: n_spec, n_exti, DT [n_bins]")
+        self.n_bins = int(self.DT.numel())
+        self.origin, self.present, self.init_death = float(origin), float(present), float(init_death)
+        self.m_birth, self.m_death = int(m_birth), int(m_death)
+
+
+def _mlik_temps(betas, scales):
+    b = np.ascontiguousarray(np.asarray(betas, dtype=np.float64).ravel())
+    s = np.ascontiguousarray(np.asarray(scales, dtype=np.float64).ravel())
+    if s.size != b.size:
+        raise ValueError("shape mismatch: betas, scales [T]")
+    return b, s
+
+
+def _mlik_args(data, b, s, seed, rep0, n_reps):
+    return (_hip.ptr(data.n_spec), _hip.ptr(data.n_exti), _hip.ptr(data.DT), data.n_bins, data.origin, data.present, data.m_birth,
+            data.m_death, data.init_death, b.ctypes.data_as(_hip.c_vp), s.ctypes.data_as(_hip.c_vp), int(b.size),
+            int(seed) & 0xFFFFFFFFFFFFFFFF, int(rep0), int(n_reps))
+
+
+def mlik_init(data, betas, scales, n_reps, seed, rep0=0, out=None):
+    """The initial state of replicates rep0 .. rep0 + n_reps - 1 at every temperature (lr_mlik_init) -> state [n_reps, T,
+    LR_MLIK_STATE_W] (slots: MLIK_STATE)."""
+    torch = _torch()
+    lib = _hip.load()
+    b, s = _mlik_temps(betas, scales)
+    (state,) = _ade_out(out, ((max(int(n_reps), 0), int(b.size), _hip.LR_MLIK_STATE_W),), (torch.float64,), data.device, "(state,)")
+    rc = _hip.launch(lib.lr_mlik_init, data.device, *_mlik_args(data, b, s, seed, rep0, n_reps), _hip.ptr(state))
+    _hip.check(rc, "lr_mlik_init")
+    return state
+
+
+def mlik_steps(data, betas, scales, state, it0, n_iters, s_freq, seed, rep0=0, out=None):
+    """Iterations it0 .. it0 + n_iters - 1 of every chain of `state` (updated in place; lr_mlik_steps) -> rows [n, R, T,
+    LR_MLIK_ROW_W], one per chain and iteration with it % s_freq == 0 (columns: MLIK_ROW)."""
+    torch = _torch()
+    lib = _hip.load()
+    b, s = _mlik_temps(betas, scales)
+    if state.dtype != torch.float64 or state.dim() != 3 or state.shape[1] != b.size or state.shape[2] != _hip.LR_MLIK_STATE_W \
+            or not state.is_contiguous() or state.device != data.device:
+        raise ValueError("state must be mlik_init's [replicates, T, LR_MLIK_STATE_W] float64 tensor on the data's device")
+    R = int(state.shape[0])
+    n = adej_rows_needed(it0, n_iters, s_freq) if int(s_freq) >= 1 and int(n_iters) >= 0 and int(it0) >= 0 else 0
+    (rows,) = _ade_out(out, ((max(n, 0), R, int(b.size), _hip.LR_MLIK_ROW_W),), (torch.float64,), data.device, "(rows,)")
+    rc = _hip.launch(lib.lr_mlik_steps, data.device, *_mlik_args(data, b, s, seed, rep0, R), _hip.ptr(state), int(it0), int(n_iters),
+                     int(s_freq), _hip.ptr(rows) if rows.numel() else None, n)
+    _hip.check(rc, "lr_mlik_steps")
+    return rows
+
+
+def mlik_run(data, betas, scales, n_reps, n_iter, s_freq, seed, rep0=0):
+    """A whole run of the power-posterior chains: lr_mlik_init, then n_iter iterations in one launch -> (rows [n_iter / s_freq
+    rounded up, n_reps, T, LR_MLIK_ROW_W], state [n_reps, T, LR_MLIK_STATE_W]); device tensors."""
+    state = mlik_init(data, betas, scales, n_reps, seed, rep0)
+    rows = mlik_steps(data, betas, scales, state, 0, n_iter, s_freq, seed, rep0)
+    return rows, state
+
+
+def mlik_estimate(rows, betas, row0=0, n_rows=None, out=None):
+    """Stepping-stone and thermodynamic-integration estimates of log Z from rows [>= n_rows, R, T, LR_MLIK_ROW_W], rows
+    row0 .. n_rows - 1 of every chain (lr_mlik_estimate) -> MlikEstimate."""
+    torch = _torch()
+    lib = _hip.load()
+    rows = _dev(rows, torch.float64)
+    b = np.ascontiguousarray(np.asarray(betas, dtype=np.float64).ravel())
+    if rows.dim() != 4 or rows.shape[2] != b.size or rows.shape[3] != _hip.LR_MLIK_ROW_W:
+        raise ValueError("rows must be [n_rows, replicates, T, LR_MLIK_ROW_W] with T = len(betas)")
+    n = int(rows.shape[0]) if n_rows is None else int(n_rows)
+    if n > rows.shape[0]:
+        raise ValueError("rows holds fewer than n_rows rows")
+    R, T = int(rows.shape[1]), int(b.size)
+    res = _ade_out(out, ((R, max(T - 1, 0)), (R,), (R, T), (R, T), (R,), (T,)), (torch.float64,) * 6, rows.device, "MlikEstimate")
+    rc = _hip.launch(lib.lr_mlik_estimate, rows.device, _hip.ptr(rows), n, R, T, int(row0), b.ctypes.data_as(_hip.c_vp),
+                     *[_hip.ptr(t) for t in res])
+    _hip.check(rc, "lr_mlik_estimate")
+    return MlikEstimate(*res)
+
+
 EssSummary = namedtuple("EssSummary", "mean ess act se_mean stop_lag pooled_mean pooled_ess rhat n")
 EssSummary.__doc__ = """lr_ess_summary's results.  mean, ess, act (in samples), se_mean float64 and stop_lag int32: [C, K] per chain and
 column; pooled_mean, pooled_ess, rhat: [K]; n: rows kept per chain.  ESS and ACT are NaN, SE 0 and the stop lag 0 where a
