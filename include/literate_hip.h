@@ -11,7 +11,8 @@
  *   - every pointer is a DEVICE pointer (hipMalloc / torch tensor.data_ptr()) unless it is
  *     marked "host"; the caller owns every buffer, nothing is allocated behind its back;
  *   - `stream` is a hipStream_t passed as void* (NULL = default stream); every call is
- *     asynchronous on it and returns after enqueueing;
+ *     asynchronous on it and returns after enqueueing; the calls that wait for `stream` say "blocks" where they
+ *     are declared (lr_mcmc_init / _restore on some engines, lr_mcmc_time_scan, _time_steps, _status, _warnings);
  *   - return value: 0 = ok, <0 = invalid argument (LR_ERR_*), >0 = a hipError_t;
  *   - arithmetic is IEEE fp64, counts are int64 (as numpy in the reference);
  *   - results are bitwise reproducible: all reductions run in a fixed order, no float atomics;
@@ -596,7 +597,11 @@ int lr_mcmc_create(const lr_mcmc_config* cfg /* host */, const double* ts, const
 /* init_state: NULL = the CLI's initial state (K=1, Gamma(2,2) rates, LRF:580-583) drawn from the
  * chain's Philox stream; else device arrays L[C,kmax], M[C,kmax], tL[C,kmax+1], tM[C,kmax+1],
  * KL[C], KM[C] (the runMCMC argument, LRF:218).  Evaluates likA/priorA (LRF:224-230) and
- * prepares the proposal of iteration 0.                                                       */
+ * prepares the proposal of iteration 0.
+ * Not asynchronous everywhere: lr_mcmc_init and lr_mcmc_restore block until `stream` is idle on the persistent engines and on
+ * the packed scan (lr_mcmc_layout.persistent != 0 or packed_scan != 0), where they pack the lineages and read the number of
+ * packed groups back to the host; on the other engines they return after enqueueing.  Either way their work runs on
+ * `stream`, behind what the caller enqueued there (tests/test_hip_stream_contract.py).                                    */
 int lr_mcmc_init(lr_engine* e, const double* L, const double* M, const double* tL,
                  const double* tM, const int32_t* KL, const int32_t* KM, int32_t kmax, void* stream);
 int lr_mcmc_steps(lr_engine* e, int64_t n_iters, void* stream);

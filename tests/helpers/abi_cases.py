@@ -979,12 +979,12 @@ def _create_bins(times):
     return _BINS[times]
 
 
-def _make_engine(name, times, sampler, seed=11):
+def _make_engine(name, times, sampler, seed=11, table=None):
     """the engine on host-binned statistics (the binning kernel has its own case), so that the workspace is the only
-    buffer the constructor allocates through the seam"""
+    buffer the constructor allocates through the seam.  table: ENGINES, or a table with further entries (stream_cases)"""
     from literate_amd.engine import ChainEngine
     from oracle import literate_oracle as lo
-    kw, Cn, want = ENGINES[name]
+    kw, Cn, want = (table or ENGINES)[name]
     ts, te = _engine_data(times)
     common = dict(seed=seed, s_freq=S_FREQ, n_trace_slots=N_IT // S_FREQ, **kw)
     if sampler == "rj":
