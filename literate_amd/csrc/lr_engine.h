@@ -1,13 +1,14 @@
 // lr_engine.h - host-side engine object shared by the translation units of the RJMCMC engines
 // (lr_mcmc.hip: launch-based and two- / four-chain persistent kernels, lr_spec.hip: speculative team kernel,
-// lr_pack.hip: packing of the lineages for the persistent scans).
+// lr_pack.hip: packing of the lineages for the persistent scans).  What an engine runs is decided by the planner
+// (lr_plan.h / lr_plan.hip) and kept in lr_engine.plan.
 #pragma once
 #include <cmath>
 #include "lr_internal.h"
+#include "lr_plan.h"
 #include "lr_scan.h"
 #include "lr_step.h"
 
-#define LR_MAX_PARTS 4
 // a partition = a contiguous, independent block of chains with its own stream and captured graph; inside it
 // the chains are software-pipelined in two halves (A = [base, base+hA), B = the rest)
 struct lr_part {
@@ -30,15 +31,13 @@ struct lr_p4_shares {
 struct lr_engine {
     lr_mcmc_config cfg;
     lr_mcmc_layout lay;
-    lr_scan_plan plan;
+    lr_engine_plan plan;      // what runs, as lr_plan_engine decided it for cfg (lr_mcmc_create plans once, through lr_plan_layout)
     const double* ts;
     const double* te;
     const double* br_length;
     char* ws;
     bool initialised;
-    int n_parts;
-    lr_part part[LR_MAX_PARTS];
-    bool persistent;          // use lr_persist_kernel in lr_mcmc_steps
+    lr_part part[LR_MAX_PARTS];   // the plan's partitions with their streams and graphs: launch-based engines only (plan.family == 0)
     long long n8;             // 16-byte groups of packed lineage indices
     long long n8_alloc;       // ... allocated (zero-filled behind the data)
     lr_p4_shares p4;          // per scanner wave: trips more (+) or fewer (-) than the equal share (four-chain kernel)
@@ -47,54 +46,22 @@ struct lr_engine {
     int p4_cfg;               // ... and its configuration word (LR_P4_CFG_*, lr_p4_cfg_choice), latched with p4_help
     bool p4_resident;         // ... and whether its scanning lanes keep decoded groups in registers (lr_p4_resident_choice), latched with p4_help
     bool packed_scan;         // launch-based engine whose scan kernel reads the PACKED lineages (lr_packscan.hip) instead of ts / te:
-                              // planned by lr_mcmc_query_layout (lay.packed_scan), dropped by init / restore if the packing
+                              // planned (plan.packed_scan), dropped by init / restore if the packing
                               // refuses the input (unsorted beyond LR_MAX_RUNS runs)
-    bool streaming;           // launch-based plan, but the iterations run inside ONE resident kernel (lr_stream.hip): latched by
-                              // lr_mcmc_create, which asks the device in use whether the whole grid fits it at once
+    bool streaming;           // launch-based plan, but the iterations run inside ONE resident kernel (lr_stream.hip): wanted by the
+                              // plan (plan.streaming), latched by lr_mcmc_create, which asks the device in use whether the whole grid fits it at once
     hipEvent_t fork;
     hipEvent_t ev0, ev1;      // timing events of lr_mcmc_time_steps / lr_mcmc_time_scan, created once
 };
 
 
-// spare zero-filled 16-byte groups behind the packed lineages (group 0 bytes = sentinel table entries, contribution 0):
-// room for the trips the four-chain kernel moves between waves and for its prefetch past the end
-#define LR_P4_MAX_GIVE 64
-// sized for the widest stride (16 scanner waves x 64 lanes): the takers' extra trips reach group (k_tot + give) * stride
-#define LR_IDX_SPARE ((LR_P4_MAX_GIVE + 2) * 1024)
-// the packing keeps the caller's order and starts a new group wherever the birth bin changes: lineages sorted by birth
-// time give at most n_bins + 2 such runs; more than LR_MAX_RUNS of them (unsorted input) are refused
-#define LR_MAX_RUNS (1ll << 20)
-
-static inline long long lr_groups_alloc(long long n_lineages) {
-    const long long runs = n_lineages < LR_MAX_RUNS ? n_lineages : LR_MAX_RUNS;
-    // (unit resolution: LR_SLOTS slots of one or two lineages per group - all singles in the worst case)
-    return (n_lineages + LR_SLOTS - 1) / LR_SLOTS + runs + LR_IDX_SPARE;
-}
-
-// four-chain kernel: bytes per block of the sums a launch leaves for the next ([16 waves][2] doubles + a valid word)
-#define LR_P4_CARRY_BYTES 512
-
-// widest table class of the persistent kernels (the launch-based scans are instantiated up to H = 264)
-#define LR_H_WIDE 520
-
 // ---- speculative team engine (lr_spec.h / lr_spec.hip) ----
-#ifndef LR_SPEC_THREADS
-#define LR_SPEC_THREADS 768   /* a team per pair: 12 waves = 4 candidate + 8 scanner waves, 3 per SIMD = 168 VGPRs each */
-#endif
-#ifndef LR_SPEC_THREADS_SINGLE
-#define LR_SPEC_THREADS_SINGLE 768    /* a team per chain: 12 waves = 2 candidate + 2 helper + 8 scanner waves.  (1024 threads = 12
-                                         scanner waves fit without spills - with the table build on the helper waves no role needs
-                                         more than ~105 VGPRs - and take 5 % off a 100k-lineage scan on one CU, but every team
-                                         exchange and every short scan got 3-8 % slower: measured round 3, not used) */
-#endif
 #ifndef LR_SPEC_SCAN_UNROLL
 #define LR_SPEC_SCAN_UNROLL 1
 #endif
 #ifndef LR_SPEC_SCAN_PRIO
 #define LR_SPEC_SCAN_PRIO 2   /* s_setprio of the scanner waves of a team (0 = leave the default) */
 #endif
-#define LR_TEAM_MAX 8
-#define LR_SPEC_GRANULES 16      /* 8-byte granules reserved per block and parity: one 128-byte line */
 #define LR_SPEC_TIMEOUT_TICKS 200000000ull   /* 2 s of the 100 MHz wall clock */
 
 // Four-chain kernel: helper waves (lr_persist4_kernel's HELP) under the RJ sampler at unit resolution; LR_P4_HELP = 0: the
@@ -102,7 +69,7 @@ static inline long long lr_groups_alloc(long long n_lineages) {
 // (a test process that runs both forms re-initialises between them); everything else reads e->p4_help.
 static inline bool lr_p4_help_choice(const lr_engine* e) {
     const char* env = getenv("LR_P4_HELP");
-    if (e->lay.persistent != 2 || e->plan.unit == LR_TAB_PAIRGEN || e->cfg.sampler != 0 || e->plan.H > 264) return false;
+    if (e->lay.persistent != 2 || e->plan.scan.unit == LR_TAB_PAIRGEN || e->cfg.sampler != 0 || e->plan.scan.H > 264) return false;
     return env ? atoi(env) != 0 : true;
 }
 
@@ -144,9 +111,8 @@ static inline int lr_spec_mode(const lr_engine* e) {
 
 // ---- resident streaming engine (lr_stream.hip) ----
 #define LR_STEP_WAVES_PER_BLOCK (LR_SCAN_THREADS / LR_WAVE)
-// counters of one launch, in the workspace at lr_mcmc_layout.xchg, each on a cache line of its own; the second table buffer
-// follows LR_STREAM_SYNC_BYTES behind
-#define LR_STREAM_COPIES 64
+// counters of one launch, in the workspace at lr_mcmc_layout.xchg, each on a cache line of its own (LR_STREAM_COPIES,
+// LR_STREAM_SYNC_BYTES: lr_plan.h)
 #define LR_STREAM_MAX_CHAINS 16
 struct lr_stream_sync {
     unsigned long long arrived;      // scanner blocks that have stored their tile's partial sums, over the launch's iterations
@@ -160,16 +126,11 @@ struct lr_stream_sync {
     //               that staged the early tables stages again if this moved since
     unsigned long long word[LR_STREAM_COPIES][LR_STREAM_MAX_CHAINS];
 };
-#define LR_STREAM_SYNC_BYTES (128 + LR_STREAM_COPIES * 128 + 128)
 static_assert(sizeof(lr_stream_sync) + 128 == LR_STREAM_SYNC_BYTES && LR_STREAM_SYNC_BYTES % 256 == 0, "counter line + a line per copy");
-bool lr_stream_eligible(const lr_mcmc_config* cfg, const lr_scan_plan& p);
-void lr_stream_plan(const lr_mcmc_config* cfg, lr_scan_plan* p, int cus);
 // n_iters iterations in launches of at most 4096; query = true only asks whether the grid fits the current device at once
 int lr_launch_stream(lr_engine* e, const lr_step_args& a, int64_t n_iters, bool query, hipStream_t stream);
 
 // ---- packed scan of the launch-based engine (lr_packscan.hip) ----
-bool lr_packscan_eligible(const lr_mcmc_config* cfg, const lr_scan_plan& p);
-void lr_packscan_plan(const lr_mcmc_config* cfg, lr_scan_plan* p, int cus);
 int lr_packscan_pairs(const lr_scan_plan& p, int n_chains);
 int lr_launch_packscan(const lr_engine* e, int base, int count, hipStream_t stream);
 
@@ -177,6 +138,5 @@ int lr_launch_packscan(const lr_engine* e, int base, int count, hipStream_t stre
 lr_step_args lr_make_args(const lr_engine* e);
 // lr_pack.hip: (re)builds the packed lineages in the workspace and the scanner-wave shares; blocks on `stream` once
 int lr_pack_lineages(lr_engine* e, hipStream_t stream);
-long long lr_pack_tmp_bytes(long long n_lineages);
 // lr_spec.hip: n_iters iterations of the speculative team kernel
 int lr_launch_spec(lr_engine* e, const lr_step_args& a, const lr_packed_lineages& pk, int64_t n_iters, hipStream_t stream);

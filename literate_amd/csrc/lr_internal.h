@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 #include "../../include/literate_hip.h"
 
@@ -49,6 +50,13 @@ int lr_launch_build_tables(const double* lam_bins, const double* mu_bins, const 
 static inline bool lr_fused_supported(const lr_scan_plan& p) {
     if (!p.fast) return false;
     return p.unit ? (p.cb == 16 || p.cb == 8) : (p.cb == 8 || p.cb == 4);
+}
+
+// an integer switch from the environment (A/B runs, tests); where a caller keeps the value in a function-local static it is
+// latched at first use
+static inline int lr_env_int(const char* name, int dflt) {
+    const char* v = getenv(name);
+    return v ? atoi(v) : dflt;
 }
 
 static inline int lr_align_up(long long x, long long a) { return (int)((x + a - 1) / a * a); }

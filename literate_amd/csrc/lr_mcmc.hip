@@ -946,445 +946,17 @@ __global__ __launch_bounds__(LR_WAVE) void lr_chain_init_kernel(lr_step_args a, 
 }
 
 // ---- host -------------------------------------------------------------------------------
-static int lr_env_int(const char* name, int dflt) {
-    const char* v = getenv(name);
-    return v ? atoi(v) : dflt;
-}
-static int lr_pipeline_env() {
-    static int env = lr_env_int("LR_PIPELINE", 1);
-    return env;
-}
-
-// The launch-based engine scans the PACKED lineages (lr_packscan.hip) where that applies and pays: always with too few chains
-// for the pipelined schedule; with more, once a pass is long against the chain step it no longer hides (the packed scan runs
-// at ~3e13 evals/s - the pipelined launches on ts / te at 7e12 - but serially before the step kernel)
-// (p: the plan with the PAIR tables the packed scan reads - unit resolution: the launches' own; general times: the
-// pair-general layout of the persistent engines, 32-bit fixed-point fractions)
-static bool lr_packscan_planned(const lr_mcmc_config* cfg, const lr_scan_plan& p) {
-    if (!lr_packscan_eligible(cfg, p)) return false;
-    const bool general = p.unit == LR_TAB_PAIRGEN;
-    const double evals = (double)cfg->n_lineages * (double)cfg->n_chains;
-    // (chains that the launches on ts / te would not pipeline either: fewer than two blocks' worth - general times: up to the
-    // sixteen of the wide scan)
-    return cfg->engine_mode == 7 || cfg->n_chains < (general ? 17 : 32) || evals >= (general ? 1.5e8 : 3.0e8);
-}
-
-// 0: the launches scan ts / te; 1: the packed lineages in one partition; 2: ... in partitions (long scans)
-static int lr_packed_mode(const lr_mcmc_config* cfg, const lr_scan_plan& p) {
-    if (!lr_packscan_planned(cfg, p)) return 0;
-    const char* env = getenv("LR_PACKED_PARTS");          // 1 / 2 force it (read per call: tests switch it)
-    if (env && (atoi(env) == 1 || atoi(env) == 2)) return atoi(env);
-    const double evals = (double)cfg->n_lineages * (double)cfg->n_chains;
-    // (scratch/exp_packed_parts.py: a tie at n C = 3.2e8, two partitions 3-7 % ahead at 3.8e8 - 6.4e8, 8-16 % beyond; general
-    // times cost twice the gathers per eval)
-    return evals >= (p.unit == LR_TAB_PAIRGEN ? 1.75e8 : 3.5e8) ? 2 : 1;
-}
-
-// Partition layout of the engine.  LR_PARTS (default 2) independent partitions run on their own streams so
-// that the ramp-up / drain of one partition's launches overlaps the other's; each partition with at least
-// 2*cb chains is software-pipelined in two halves.  All boundaries are multiples of cb.
-// packed (lr_packed_mode): the launches scan the packed lineages - never pipelined (one launch scores a group against all
-// chains of its partition); 2: partitions on their own streams overlap one's step kernel with the other's scan, 1: one
-// partition (short scans: two streams of 5-us kernels do not overlap well - 16 chains x 1e7 lineages 20.9 us per iteration in
-// two partitions against 16.4 in one; x 1e8: 54.1 against 63.9)
-static int lr_partition(int n_chains, int cb, bool fused_ok, int base[LR_MAX_PARTS + 1], int hA[LR_MAX_PARTS],
-                        bool pipelined[LR_MAX_PARTS], int packed = 0) {
-    static const int want_parts = lr_env_int("LR_PARTS", 2);
-    int parts = want_parts < 1 ? 1 : (want_parts > LR_MAX_PARTS ? LR_MAX_PARTS : want_parts);
-    if (packed) fused_ok = false;
-    if (packed == 1) parts = 1;
-    const int groups = (n_chains + cb - 1) / cb;
-    const bool pipe = lr_pipeline_env() && fused_ok;
-    while (parts > 1 && groups < parts * (pipe ? 2 : 1)) --parts;
-    base[0] = 0;
-    for (int p = 0; p < parts; ++p) {
-        const int g = groups / parts + (p < groups % parts ? 1 : 0);
-        base[p + 1] = base[p] + g * cb < n_chains ? base[p] + g * cb : n_chains;
-    }
-    base[parts] = n_chains;
-    for (int p = 0; p < parts; ++p) {
-        const int count = base[p + 1] - base[p];
-        pipelined[p] = pipe && count >= 2 * cb;
-        hA[p] = pipelined[p] ? ((count / 2 + cb - 1) / cb) * cb : count;
-    }
-    return parts;
-}
-
-// launch shape of the engine: as lr_plan_scan, but when the pipelined schedule applies the lineage tiles are
-// sized so that the fused launches that run concurrently (one per partition: step blocks of one half + scan
-// blocks of the other) fill the resident block slots of the chip (256 CUs x 4 blocks) exactly once.
-static int lr_persist_variant(const lr_mcmc_config* cfg, const lr_scan_plan& p, int* team_k, int* team_cpb);
-static int lr_device_cus();
-static int lr_plan_engine(const lr_mcmc_config* cfg, lr_scan_plan* p) {
-    // (general times, 9 to 16 chains: ONE pass of the sixteen-chain scan - lr_scan_wide_kernel - instead of two halves of eight)
-    int rc = lr_plan_scan(cfg->n_lineages, cfg->n_chains, cfg->n_bins, cfg->model, cfg->unit_resolution, p,
-                          (!cfg->unit_resolution && cfg->n_chains > 8 && cfg->n_chains <= 16 && lr_env_int("LR_ENGINE_WIDE", 1)) ? 1 : 0);
-    if (rc) return rc;
-    if (cfg->model == LR_MODEL_KEIDING_DEAD && cfg->n_bins <= 258) {
-        // model 3 on a persistent engine: one table class with an extant block behind the death-side entries (lr_step.h),
-        // so the half-stride must hold 2 (n_bins + 2) entries
-        static const int fast_H[] = {40, 72, 136, 264, LR_H_WIDE};
-        lr_scan_plan q = *p;
-        q.n_cls = 1, q.fast = 1, q.H = 0;
-        for (int h : fast_H)
-            if (2 * (cfg->n_bins + 2) <= h) {
-                q.H = h;
-                break;
-            }
-        if (q.H) {
-            q.unit = cfg->unit_resolution ? LR_TAB_UNIT : LR_TAB_PAIRGEN;
-            q.cb = cfg->unit_resolution ? 16 : 4;
-            while (q.unit == LR_TAB_UNIT && q.cb > 2 && q.cb / 2 >= cfg->n_chains) q.cb >>= 1;
-            q.tab_stride = q.unit == LR_TAB_UNIT ? q.H : 2 * q.H;
-            q.groups = (cfg->n_chains + q.cb - 1) / q.cb;
-            if (lr_persist_variant(cfg, q, nullptr, nullptr) != 0) {
-                *p = q;
-                return LR_OK;
-            }
-            // ... or, on the same tables, under the launch-based engine scanning the packed lineages (their death-side slots
-            // point extant lineages at the extant block)
-            if (lr_packscan_planned(cfg, q)) {
-                *p = q;
-                lr_packscan_plan(cfg, p, lr_device_cus());
-                return LR_OK;
-            }
-        }
-    }
-    if (!p->unit && p->fast && p->n_cls == 1) {
-        // general lineage times: a persistent engine takes them in the pair-general table layout (LR_TAB_PAIRGEN) with the
-        // in-bin fractions packed as 32-bit fixed point; if none applies the plan stays the launch-based engine's
-        lr_scan_plan q = *p;
-        q.unit = LR_TAB_PAIRGEN, q.cb = 4;
-        q.groups = (cfg->n_chains + q.cb - 1) / q.cb;
-        if (lr_persist_variant(cfg, q, nullptr, nullptr) != 0) {
-            *p = q;
-            return LR_OK;
-        }
-        // ... or the launch-based engine scanning the packed lineages, on the same pair-general tables
-        if (lr_packscan_planned(cfg, q)) {
-            *p = q;
-            lr_packscan_plan(cfg, p, lr_device_cus());
-            return LR_OK;
-        }
-    }
-    if (!p->fast && cfg->model != LR_MODEL_KEIDING_DEAD && cfg->n_bins + 2 <= LR_H_WIDE && cfg->n_bins <= 64 * lr_bins_per_lane(LR_H_WIDE)) {
-        // 255..512 bins: beyond the table sizes the launch-based scans are instantiated for, but the persistent kernels
-        // (two- and four-chain; the packed groups address their entries with 16 bits) take one more class, H = 520;
-        // the scans outside the kernels go through lr_pairscan_kernel as they do for pair-general tables
-        lr_scan_plan q = *p;
-        q.n_cls = 1, q.fast = 1, q.H = LR_H_WIDE;
-        q.unit = cfg->unit_resolution ? LR_TAB_UNIT : LR_TAB_PAIRGEN;
-        q.cb = cfg->unit_resolution ? 16 : 4;
-        while (q.unit == LR_TAB_UNIT && q.cb > 2 && q.cb / 2 >= cfg->n_chains) q.cb >>= 1;
-        q.tab_stride = q.unit == LR_TAB_UNIT ? q.H : 2 * q.H;
-        q.groups = (cfg->n_chains + q.cb - 1) / q.cb;
-        if (lr_persist_variant(cfg, q, nullptr, nullptr) != 0) {
-            *p = q;
-            return LR_OK;
-        }
-        // ... or the launch-based engine scanning the packed lineages (two pairs of H = 520 tables per block)
-        if (lr_packscan_planned(cfg, q)) {
-            *p = q;
-            lr_packscan_plan(cfg, p, lr_device_cus());
-            return LR_OK;
-        }
-    }
-    int base[LR_MAX_PARTS + 1], hA[LR_MAX_PARTS];
-    bool pipelined[LR_MAX_PARTS];
-    const bool packed = lr_packscan_planned(cfg, *p);
-    const int parts = lr_partition(cfg->n_chains, p->cb, lr_fused_supported(*p), base, hA, pipelined, lr_packed_mode(cfg, *p));
-    if (!pipelined[0]) {
-        // the scan over the packed lineages (unit resolution), or - too few chains for two halves, opt-in - the resident
-        // streaming kernel, its tiles sized to the device's block slots
-        if (packed) lr_packscan_plan(cfg, p, lr_device_cus());
-        else if (parts == 1 && lr_stream_eligible(cfg, *p)) lr_stream_plan(cfg, p, lr_device_cus());
-        return LR_OK;
-    }
-    const int count = base[1] - base[0];
-    const int half = hA[0] > count - hA[0] ? hA[0] : count - hA[0];
-    const int groups_half = (half + p->cb - 1) / p->cb;
-    const int step_blocks = (half + (LR_SCAN_THREADS / LR_WAVE) - 1) / (LR_SCAN_THREADS / LR_WAVE);
-    static const int slots = lr_env_int("LR_SLOTS", 256 * 4);
-    long long tiles = (slots / parts - step_blocks) / groups_half;
-    const long long unit = 2 * LR_SCAN_THREADS;
-    const long long max_tiles = (cfg->n_lineages + 4 * unit - 1) / (4 * unit);
-    if (tiles > max_tiles) tiles = max_tiles;
-    if (tiles < 1) tiles = 1;
-    long long chunk = lr_align_up64((cfg->n_lineages + tiles - 1) / tiles, unit);
-    tiles = (cfg->n_lineages + chunk - 1) / chunk;
-    p->tiles = (int)tiles;
-    p->chunk = chunk;
-    return LR_OK;
-}
-
-// Compute units of the CURRENT device (the engine is planned and created with its device current: literate_amd/engine.py),
-// asked every time: a process may drive several devices.  LR_DEVICE_CUS overrides it (planner tests).  Without a device
-// to ask (planning on a GPU-less host: the CPU tests) an MI355X is assumed - lr_mcmc_create cannot succeed there anyway.
-static int lr_device_cus() {
-    const char* v = getenv("LR_DEVICE_CUS");
-    if (v && atoi(v) > 0) return atoi(v);
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) return n;
-    return 256;
-}
-
-// Speculative team kernel (lr_spec.h): one block per CU, a chain pair - or a single chain - owned by a team of k blocks.
-// Model of an iteration in microseconds, fitted to MI355X measurements over 1k..200k lineages x k = 1, 2, 4, 8 x chains per
-// team (scratch/exp_teams.py, round 3: candidates with a column of their own, no-op moves copying it): with `trips` =
-// groups / k / 512 scanner lanes,
-//                        a team per PAIR                                  a team per CHAIN
-//     unit resolution    k = 1: max(2.95, 2.93 + 0.180 trips)             k = 1: max(2.02, 1.68 + 0.135 trips)
-//                        k > 1: max(3.40, 3.20 + 0.205 trips)             k > 1: max(2.78, 2.32 + 0.125 trips) + 0.05 log2(k / 2)
-//     general times      k = 1: max(2.90, 2.85 + 0.434 trips)             k = 1: max(2.05, 1.53 + 0.30 trips)
-//                        k > 1: max(3.45, 2.90 + 0.478 trips)             k > 1: max(2.63, 2.15 + 0.33 trips) + 0.05 log2(k / 2)
-//     DDRate / trend     k = 1: max(2.60, 2.70 + 0.18 trips)              k = 1: max(2.05, 1.55 + 0.125 trips)
-//                        k > 1: max(3.05, 2.70 + 0.21 trips)              k > 1: max(2.90, 2.25 + 0.112 trips)
-// (a team per chain: refitted in round 4 to the one-chain form of the scan - 8-byte gathers, half the fp64 instructions -,
-// scratch/exp_teams.py 1 unit | dd | general on 32 chains; LR_PLAN_CHECK=1 checks the choice on the device in use)
-// (the floor is the candidate build - shorter with one chain per CU: the table is built by a helper wave on a SIMD of its
-// own, a no-op move copies its table, and the scanners need no table build behind the barrier -; a team pays the exchange
-// behind its last scanner; a team per chain scans for one chain what a team per pair scans for two, so it needs the CUs:
-// chains x k <= CUs).  Returns the modelled time, the best team size in *k
-// (0 = not applicable) and the chains per team.
-static double lr_spec_model(const lr_mcmc_config* cfg, int* k_out, bool general = false, int* cpb_out = nullptr) {
-    const int cus = lr_device_cus();
-    *k_out = 0;
-    if (cpb_out) *cpb_out = 2;
-    static const int k_env0 = lr_env_int("LR_SPEC_TEAM", 0);
-    // (lr_check_cfg has refused a request that is not 1, 2, 4 or 8; a malformed LR_SPEC_TEAM is ignored)
-    const int k_req = cfg->team_request & 0xff, cpb_req = (cfg->team_request >> 8) & 0xff;
-    const int k_env = k_req > 0 ? k_req : ((k_env0 == 1 || k_env0 == 2 || k_env0 == 4 || k_env0 == 8) ? k_env0 : 0);
-    static const int cpb_env0 = lr_env_int("LR_SPEC_CPB", 0);       // 1 / 2 force the chains per team (A/B runs)
-    const int cpb_env = cpb_req > 0 ? cpb_req : cpb_env0;
-    const double n8 = (double)((cfg->n_lineages + LR_GRP - 1) / LR_GRP);      // groups, for lineages sorted by birth time
-    double best = 1e30;
-    for (int cpb = 1; cpb <= 2; ++cpb) {
-        if (cpb_env != 0 && cpb != cpb_env) continue;
-        const int teams = (cfg->n_chains + cpb - 1) / cpb;
-        if (teams > cus) continue;
-        double best_c = 1e30;
-        int k_c = 0;
-        for (int k = 1; k <= LR_TEAM_MAX; k *= 2) {
-            if (teams * k > cus) break;
-            if (k_env > 0 && k != k_env) continue;
-            // (groups beyond an XCD's 4 MB of L2 stream from HBM with one group of prefetch per lane: measured 0.32 instead of
-            // 0.205 us per trip at 10M lineages; round-2 sweep)
-            // (... setting in gradually: 1e6 lineages on general times - 4.6 MB of groups and fractions - ran 8.9 us per
-            // iteration of 16 chains where the full penalty predicted 14.7 and the planner took the launches at 15.1: the
-            // round-5 sweep, profiles/r05_packed_scan.txt)
-            const double over = n8 * 16.0 * (general ? 1.0 + LR_FRAC_ARRAYS : 1.0) / 4.0e6 - 1.0;
-            const double sfrac = over <= 0.0 ? 0.0 : (over >= 1.0 ? 1.0 : over);
-            const bool streaming = sfrac >= 0.5;
-            const double slow = 1.0 + 0.55 * sfrac;
-            const double trips = slow * n8 / k / (double)((cpb == 1 ? LR_SPEC_THREADS_SINGLE : LR_SPEC_THREADS) - 256);
-            // (a trip that waits for its group to arrive from HBM costs what the memory round trip costs: the one-chain form
-            // of the scan, which made the L2-resident trips of a team per chain cheaper in round 4, does not shorten it -
-            // the round-3 slopes stay for that regime)
-            const double s1 = streaming ? 0.20 : 0.135, sk = streaming ? 0.165 : 0.125;          // unit resolution, a team per chain
-            const double d1 = streaming ? 0.20 : 0.125, dk = streaming ? 0.16 : 0.112;           // parametric samplers
-            const double g1 = streaming ? 0.46 : 0.30, gk = streaming ? 0.46 : 0.33;             // general times
-            double t;
-            if (cfg->sampler != 0) {
-                if (cpb == 2) t = (k == 1) ? fmax(2.60, 2.70 + 0.18 * trips) : fmax(3.05, 2.70 + 0.21 * trips);
-                else t = (k == 1) ? fmax(2.05, 1.55 + d1 * trips) : fmax(2.90, 2.25 + dk * trips);
-                if (general) t += ((cpb == 1 && !streaming) ? 0.17 : 0.26) * trips;
-            } else if (!general) {
-                if (cpb == 2) t = (k == 1) ? fmax(2.95, 2.93 + 0.180 * trips) : fmax(3.40, 3.20 + 0.205 * trips);
-                else t = (k == 1) ? fmax(2.02, 1.68 + s1 * trips) : fmax(2.78, 2.32 + sk * trips) + (k == 4 ? 0.05 : (k == 8 ? 0.10 : 0.0));
-            } else {
-                if (cpb == 2) t = (k == 1) ? fmax(2.90, 2.85 + 0.434 * trips) : fmax(3.45, 2.90 + 0.478 * trips);
-                else t = (k == 1) ? fmax(2.05, 1.53 + g1 * trips) : fmax(2.63, 2.15 + gk * trips) + (k == 4 ? 0.05 : (k == 8 ? 0.10 : 0.0));
-            }
-            if (t < best_c - 0.05) best_c = t, k_c = k;
-        }
-        if (k_c > 0 && best_c < best) {
-            best = best_c, *k_out = k_c;
-            if (cpb_out) *cpb_out = cpb;
-        }
-    }
-    return best;
-}
-
-// Persistent engine (lr_persist_kernel): needs unit-resolution tables with byte-sized indices and an
-// instantiated table size.  cfg->engine_mode 1 / 2 / 3 force the launch-based / persistent / four-chain persistent
-// engine (2 and 3 still need the prerequisites); auto picks the persistent kernel unless the chains are too few for the lineage count: a block
-// scans ALL lineages for its two chains, so with few chains and very long inputs the tiled launch-based scan,
-// which spreads one chain group over many CUs, is faster.
-// Measured iteration times (us, MI355X, scratch/exp_p2_vs_p4.py: 3k..3M lineages x 768 / 1024 / 1536 chains; refitted at
-// the end of round 3, the four-chain kernel with helper waves) of the two persistent kernels that take more than 256
-// chain pairs, per round of 1024 chains:
-//   two-chain kernel (512-thread blocks, two per CU)   f2 = 4.8 + 0.0355 per 1000 lineages
-//   four-chain kernel                                  f4 = max(5.45, 3.13 + 0.0362 per 1000 lineages)
-//                                                      (general times: max(8.0, 3.8 + 0.091 per 1000 lineages), round 2)
-// and a remainder of at most 512 chains costs the two-chain kernel 0.62 of a round.
-static double lr_model_two_chain(const lr_mcmc_config* cfg) {
-    const double kn = (double)cfg->n_lineages * 1e-3;
-    const int C = cfg->n_chains, rem = C % 1024;
-    const double f2 = 4.8 + 0.0355 * kn;
-    return f2 * ((double)(C / 1024) + (rem == 0 ? 0.0 : (rem <= 512 ? 0.62 : 1.0)));
-}
-static double lr_model_four_chain(const lr_mcmc_config* cfg, bool general) {
-    const double kn = (double)cfg->n_lineages * 1e-3;
-    const double f4 = general ? fmax(8.0, 3.8 + 0.091 * kn) : fmax(5.45, 3.13 + 0.0362 * kn);
-    return f4 * (double)((cfg->n_chains + 1023) / 1024);
-}
-
-static bool lr_persist_eligible(const lr_mcmc_config* cfg, const lr_scan_plan& p) {
-    static const int env = lr_env_int("LR_PERSIST", -1);   // debugging override: 0 off, 1 on
-    if (env == 0 || cfg->engine_mode == 1 || cfg->engine_mode == 6 || cfg->engine_mode == 7) return false;
-    if (!p.unit || cfg->n_bins + 2 > LR_H_WIDE || p.cb < 2) return false;
-    const bool general = p.unit == LR_TAB_PAIRGEN;
-    // the packing holds lineage indices as int32 and the scan loops address the groups by 32-bit byte offsets
-    if (cfg->n_lineages >= (1ll << 31) - 1 || lr_groups_alloc(cfg->n_lineages) * 16 >= (1ll << 32)) return false;
-    if (p.H != 40 && p.H != 72 && p.H != 136 && p.H != 264 && p.H != LR_H_WIDE) return false;
-    if (env == 1 || cfg->engine_mode >= 2) return true;
-    const double n = (double)cfg->n_lineages, c = (double)cfg->n_chains;
-    // the best persistent kernel for the shape (microseconds) against the tiled launches (measured: 7e12 evals/s at unit
-    // resolution, 3e12 on general times, 15.5 us of launches per iteration + 1 us per 1024 chains of the step blocks:
-    // scratch/exp_plan_small.py - with a flat 14 us, 4096 chains on short inputs went to the launches at 19.5 - 23 us
-    // where the two-chain kernel runs 15.7 - 19.1)
-    double t_persist = lr_model_four_chain(cfg, general);
-    if (!general) t_persist = fmin(t_persist, lr_model_two_chain(cfg));
-    int k = 0;
-    const double t_spec = (p.H > (general ? 136 : 264)) ? 1e30 : lr_spec_model(cfg, &k, general);   // few chains: a team of CUs per pair
-    if (k > 0 && t_spec < t_persist) t_persist = t_spec;
-    double t_launch = n * c / (general ? 3e12 : 7e12) * 1e6 + 15.5 + c / 1024.0;
-    // ... or, at unit resolution, one launch over the packed lineages for all chains + the step kernel (16 chains x 1e7 / 3e7 /
-    // 1e8 lineages: 16.3 / 27.0 / 63.9 us per iteration, scan alone 9.6 / 19.7 / 55.8: round 5)
-    // (general times: sixteen gathers per group and pair instead of eight)
-    // (only where the launches WOULD scan the packed lineages: lr_packscan_planned)
-    if (lr_packscan_planned(cfg, p)) t_launch = fmin(t_launch, 11.5 + 5.0 * c / 1024.0 + n * c / (general ? 1.5e13 : 3.1e13) * 1e6);
-    return t_persist <= t_launch;
-}
-
-// Which persistent kernel: 1 = two chains per 512-thread block (lr_persist_kernel), 2 = four chains per 1024-thread
-// block in ping-pong (lr_persist4_kernel), 3 = the speculative team kernel (at most 256 chain pairs).  The four-chain
-// block hides the chain step under the other pair's scan, so beyond 256 pairs it wins while a scan is about as long as a
-// step (from ~20k lineages up, whole rounds of 1024 chains); the two-chain kernel, two blocks per CU, is ahead on short
-// scans (the step is all there is) and on remainders of at most 512 chains; on very long scans the two tie.
-static int lr_persist_variant(const lr_mcmc_config* cfg, const lr_scan_plan& p, int* team_k, int* team_cpb = nullptr) {
-    if (team_k) *team_k = 0;
-    if (team_cpb) *team_cpb = 0;
-    if (!lr_persist_eligible(cfg, p)) return 0;
-    static const int p4_env = lr_env_int("LR_PERSIST4", -1);
-    static const int spec_env = lr_env_int("LR_SPEC", -1);
-    const bool general = p.unit == LR_TAB_PAIRGEN;   // general times: the speculative (H <= 136) and four-chain kernels only
-    int k = 0, cpb = 2;
-    const double t_spec = (p.H > (general ? 136 : 264)) ? 1e30 : lr_spec_model(cfg, &k, general, &cpb);
-    if (k > 0 && t_spec < 1e29 && cfg->engine_mode != 3 && cfg->engine_mode != 4 && spec_env != 0) {
-        // the two-chain kernel with all 16 waves scanning wins only on long scans without room for a team
-        // (measured at 256 pairs, 10k..1M lineages, scratch/exp_engines.py: 4.41 + 0.236 us per trip of its 1024 scanner
-        // lanes, 4.1 at least; the speculative kernel is ahead up to ~200k lineages)
-        const double t_wide = general ? 1e30 : fmax(4.1, 4.41 + 0.236 * (double)((cfg->n_lineages + LR_GRP - 1) / LR_GRP) / 1024.0);
-        if (cfg->engine_mode == 5 || spec_env == 1 || t_spec <= t_wide) {
-            if (team_k) *team_k = k;
-            if (team_cpb) *team_cpb = cpb;
-            return 3;
-        }
-    }
-    if (cfg->engine_mode == 5) return 0;
-    if (general) return (p.cb >= 4 && cfg->engine_mode != 4) ? 2 : 0;
-    if (p.cb < 4) return 1;                 // tables are laid out per group of cb chains; a quad must not straddle
-    if (cfg->engine_mode == 3) return 2;
-    if (cfg->engine_mode == 4) return 1;
-    if (p4_env >= 0) return p4_env ? 2 : 1;
-    return lr_model_four_chain(cfg, false) < lr_model_two_chain(cfg) ? 2 : 1;
-}
-
-static int lr_check_cfg(const lr_mcmc_config* cfg) {
-    if (!cfg) return LR_ERR_NULL;
-    if (cfg->n_lineages < 1 || cfg->n_chains < 1 || cfg->s_freq < 1 || cfg->n_trace_slots < 0) return LR_ERR_SIZE;
-    if (cfg->n_bins < 1 || cfg->n_bins > LR_MAX_BINS) return LR_ERR_SIZE;
-    if (cfg->model < 0 || cfg->model > 3) return LR_ERR_MODEL;
-    if (cfg->t0 != floor(cfg->t0)) return LR_ERR_T0;
-    if (!(cfg->end_time > cfg->start_time)) return LR_ERR_SIZE;
-    if (cfg->sampler < 0 || cfg->sampler > 2) return LR_ERR_MODEL;
-    {
-        const int k_req = cfg->team_request & 0xff, cpb_req = (cfg->team_request >> 8) & 0xff;
-        if (cfg->team_request < 0 || cfg->team_request > 0xffff) return LR_ERR_SIZE;
-        if (k_req != 0 && k_req != 1 && k_req != 2 && k_req != 4 && k_req != 8) return LR_ERR_SIZE;   // a team is 1, 2, 4 or 8 blocks (LR_TEAM_MAX)
-        if (cpb_req > 2) return LR_ERR_SIZE;                                                           // ... of one chain or a pair
-    }
-    if (cfg->sampler != 0) {
-        if (cfg->model != LR_MODEL_KEIDING) return LR_ERR_MODEL;
-        if (cfg->n_bins > LR_DD_MAXP * LR_WAVE) return LR_ERR_SIZE;
-    }
-    if (cfg->sampler == 1) {
-        if (cfg->m_birth < 0 || cfg->m_birth > 2 || cfg->m_death < -2 || cfg->m_death > 2) return LR_ERR_MODEL;
-        if (!(cfg->dd_present > cfg->t0)) return LR_ERR_SIZE;
-    }
-    return LR_OK;
-}
-
 extern "C" int lr_mcmc_query_layout(const lr_mcmc_config* cfg, lr_mcmc_layout* out) {
-    int rc = lr_check_cfg(cfg);
-    if (rc) return rc;
-    if (!out) return LR_ERR_NULL;
-    lr_scan_plan p;
-    rc = lr_plan_engine(cfg, &p);
-    if (rc) return rc;
-    const long long C = cfg->n_chains;
-    long long o = 0;
-    out->state_f64 = o, o += lr_align_up64(C * LR_STATE_ROWS * LR_ROW * 8, 256);
-    out->state_i32 = o, o += lr_align_up64(C * LR_ISTATE_ROWS * LR_ROW * 4, 256);
-    out->bin_consts = o, o += lr_align_up64((long long)(cfg->n_bins + 2) * 8, 256);   // log(br) + the DD constants
-    // packed lineages of the persistent engines (lr_pack.hip): groups of LR_GRP lineages of one birth bin, 16 bytes of
-    // table indices each; on general times LR_FRAC_ARRAYS more uint4 arrays with the in-bin fractions; scratch of the packing
-    const long long n_alloc = lr_groups_alloc(cfg->n_lineages);
-    out->lineage_idx = o, o += lr_align_up64(n_alloc * 16, 256);
-    out->lineage_frac = o;
-    if (p.unit == LR_TAB_PAIRGEN) o += lr_align_up64(n_alloc * 16 * LR_FRAC_ARRAYS, 256);
-    out->pack_tmp = o, o += lr_align_up64(lr_pack_tmp_bytes(cfg->n_lineages), 256);
-    out->args_blob = o, o += 1024;   // lr_step_args of the persistent kernel
-    out->tables = o, o += lr_align_up64((long long)lr_align_up64(C, p.cb < 2 ? 2 : p.cb) * p.tab_stride * 16, 256);
-    out->partials = o, o += lr_align_up64((long long)lr_tile_stride(p.tiles) * C * 8, 256);
-    out->trace = o, o += lr_align_up64((long long)cfg->n_trace_slots * C * LR_TRACE_W * 8, 256);
-    int team_k = 0, team_cpb = 0;
-    out->persistent = lr_persist_variant(cfg, p, &team_k, &team_cpb);
-    out->spec_chains_per_team = team_cpb;
-    {
-        int base[LR_MAX_PARTS + 1], hA[LR_MAX_PARTS];
-        bool pipelined[LR_MAX_PARTS];
-        const bool packed = lr_packscan_planned(cfg, p);
-        const int parts = lr_partition(cfg->n_chains, p.cb, lr_fused_supported(p), base, hA, pipelined, lr_packed_mode(cfg, p));
-        out->packed_scan = (out->persistent == 0 && packed) ? 1 : 0;
-        out->streaming = (out->persistent == 0 && !out->packed_scan && parts == 1 && !pipelined[0] && lr_stream_eligible(cfg, p)) ? 1 : 0;
-        out->reserved3 = 0;
-    }
-    if (p.unit == LR_TAB_PAIRGEN && out->persistent == 0 && !lr_packscan_planned(cfg, p)) return LR_ERR_STATE;   // (planned only when a kernel takes it)
-    out->team_blocks = team_k;
-    out->table_mode = p.unit;
-    out->status = o, o += 256;   // engine status word
-    // team exchange granules of the speculative kernel: [2 parities][pairs][LR_TEAM_MAX][LR_SPEC_GRANULES] x 8 bytes
-    // (four-chain kernel: the scan sums a launch leaves for the next one, LR_P4_CARRY_BYTES per block - lr_persist4_kernel)
-    // (streaming engine: the counters of a launch and the second table buffer)
-    out->xchg = o, o += (team_k > 1) ? lr_align_up64(2ll * C * LR_TEAM_MAX * LR_SPEC_GRANULES * 8, 256)   // (room for a team per chain)
-                                     : (out->persistent == 2 ? lr_align_up64((C + 3) / 4 * LR_P4_CARRY_BYTES, 256)
-                                        : (out->streaming ? LR_STREAM_SYNC_BYTES + lr_align_up64((long long)lr_align_up64(C, p.cb < 2 ? 2 : p.cb) * p.tab_stride * 16, 256) : 0));
-    out->total_bytes = o;
-    out->table_stride = p.tab_stride;
-    out->tiles = p.tiles;
-    out->chains_per_block = p.cb;
-    out->trace_width = LR_TRACE_W;
-    {
-        int base[LR_MAX_PARTS + 1], hA[LR_MAX_PARTS];
-        bool pipelined[LR_MAX_PARTS];
-        out->n_parts = lr_partition(cfg->n_chains, p.cb, lr_fused_supported(p), base, hA, pipelined, lr_packed_mode(cfg, p));
-        out->pipelined = pipelined[0] ? 1 : 0;
-    }
-    {
-        static const int wide_env = lr_env_int("LR_PERSIST_WIDE", -1);
-        const bool wide = wide_env >= 0 ? wide_env != 0 : ((cfg->n_chains + 1) / 2 <= 256 && cfg->n_lineages >= 20000);
-        out->reserved1 = out->persistent == 3 ? (team_cpb == 1 ? LR_SPEC_THREADS_SINGLE : LR_SPEC_THREADS) : (out->persistent == 2 ? 1024 : (out->persistent == 1 ? (wide ? 1024 : 512) : 0));   // threads per persistent block
-    }
-    return LR_OK;
+    lr_engine_plan plan;
+    return lr_plan_layout(cfg, &plan, out);
 }
 
 extern "C" int lr_mcmc_create(const lr_mcmc_config* cfg, const double* ts, const double* te, const double* br_length,
                               void* workspace, int64_t workspace_bytes, lr_engine** out) {
     if (!ts || !te || !workspace || !out) return LR_ERR_NULL;
+    lr_engine_plan plan;
     lr_mcmc_layout lay;
-    int rc = lr_mcmc_query_layout(cfg, &lay);
+    int rc = lr_plan_layout(cfg, &plan, &lay);
     if (rc) return rc;
     if ((cfg->model == LR_MODEL_BD || cfg->model == LR_MODEL_ID || cfg->sampler != 0) && !br_length) return LR_ERR_MODEL;
     if (lay.total_bytes > workspace_bytes) return LR_ERR_WORKSPACE;
@@ -1392,15 +964,10 @@ extern "C" int lr_mcmc_create(const lr_mcmc_config* cfg, const double* ts, const
     if (!e) return (int)hipErrorOutOfMemory;
     e->cfg = *cfg;
     e->lay = lay;
-    lr_plan_engine(cfg, &e->plan);
+    e->plan = plan;
     e->ts = ts, e->te = te, e->br_length = br_length;
     e->ws = (char*)workspace;
     e->initialised = false;
-    int base[LR_MAX_PARTS + 1], hA[LR_MAX_PARTS];
-    bool pipelined[LR_MAX_PARTS];
-    e->n_parts = lr_partition(cfg->n_chains, e->plan.cb, lr_fused_supported(e->plan), base, hA, pipelined,
-                              lay.packed_scan ? lr_packed_mode(cfg, e->plan) : 0);
-    e->persistent = lay.persistent != 0;
     e->n8 = 0;                                          // groups of packed lineages: known once lr_pack_lineages has run
     e->n8_alloc = lr_groups_alloc(cfg->n_lineages);
     for (int j = 0; j < 16; ++j) e->p4.delta[j] = 0;
@@ -1409,12 +976,12 @@ extern "C" int lr_mcmc_create(const lr_mcmc_config* cfg, const double* ts, const
     e->p4_cfg = lr_p4_cfg_choice(e);
     e->p4_resident = lr_p4_resident_choice(e);
     e->streaming = false;
-    e->packed_scan = lay.packed_scan != 0;
+    e->packed_scan = plan.packed_scan;
     e->fork = nullptr;
     e->ev0 = e->ev1 = nullptr;
-    for (int p = 0; p < e->n_parts; ++p) {
+    for (int p = 0; p < plan.n_parts; ++p) {
         lr_part& q = e->part[p];
-        q.base = base[p], q.count = base[p + 1] - base[p], q.hA = hA[p], q.pipelined = pipelined[p];
+        q.base = plan.base[p], q.count = plan.base[p + 1] - plan.base[p], q.hA = plan.hA[p], q.pipelined = plan.pipelined[p];
         q.stream = nullptr, q.done = nullptr, q.graph_exec = nullptr, q.graph_units = 0;
     }
     {
@@ -1427,9 +994,10 @@ extern "C" int lr_mcmc_create(const lr_mcmc_config* cfg, const double* ts, const
             return (int)he;
         }
     }
-    if (e->n_parts > 1) {
+    // (a persistent kernel takes all chains in one launch: lr_mcmc_steps never reaches the partitions' schedule, and they get no streams)
+    if (plan.family == 0 && plan.n_parts > 1) {
         hipError_t he = hipEventCreateWithFlags(&e->fork, hipEventDisableTiming);
-        for (int p = 0; p < e->n_parts && he == hipSuccess; ++p) {
+        for (int p = 0; p < plan.n_parts && he == hipSuccess; ++p) {
             he = hipStreamCreateWithFlags(&e->part[p].stream, hipStreamNonBlocking);
             if (he == hipSuccess) he = hipEventCreateWithFlags(&e->part[p].done, hipEventDisableTiming);
         }
@@ -1438,7 +1006,7 @@ extern "C" int lr_mcmc_create(const lr_mcmc_config* cfg, const double* ts, const
             return (int)he;
         }
     }
-    if (lay.streaming) {
+    if (plan.streaming) {
         // the resident kernel's blocks wait for each other: it runs only where the whole grid fits at once (LR_ERR_STATE =
         // it does not: the launches take over, same plan, same results)
         const int rcq = lr_launch_stream(e, lr_make_args(e), 0, true, nullptr);
@@ -1465,12 +1033,12 @@ lr_step_args lr_make_args(const lr_engine* e) {
     a.partials = (const double*)(e->ws + e->lay.partials);
     a.trace = (double*)(e->ws + e->lay.trace);
     a.br_length = e->br_length;
-    a.tab_stride = e->plan.tab_stride;
-    a.n_cls = e->plan.n_cls;
-    a.tiles = e->plan.tiles;
-    a.H = e->plan.H;
-    a.unit = e->plan.unit;
-    a.cb = e->plan.cb;
+    a.tab_stride = e->plan.scan.tab_stride;
+    a.n_cls = e->plan.scan.n_cls;
+    a.tiles = e->plan.scan.tiles;
+    a.H = e->plan.scan.H;
+    a.unit = e->plan.scan.unit;
+    a.cb = e->plan.scan.cb;
     a.warn = (unsigned int*)(e->ws + e->lay.status) + 1;
     return a;
 }
@@ -1480,22 +1048,22 @@ static int lr_launch_pairscan(const lr_engine* e, hipStream_t stream) {
     lr_packed_lineages pk;
     pk.idx8 = (const uint4*)(e->ws + e->lay.lineage_idx), pk.frac = (const uint4*)(e->ws + e->lay.lineage_frac);
     pk.fstride = e->n8_alloc;
-    const dim3 grid(e->plan.tiles, (e->cfg.n_chains + 1) / 2);
-    if (e->plan.unit == LR_TAB_PAIRGEN)
+    const dim3 grid(e->plan.scan.tiles, (e->cfg.n_chains + 1) / 2);
+    if (e->plan.scan.unit == LR_TAB_PAIRGEN)
         hipLaunchKernelGGL((lr_pairscan_kernel<H, true>), grid, dim3(256), 0, stream, pk, e->n8,
-                           (const double2*)(e->ws + e->lay.tables), e->cfg.n_chains, e->cfg.n_bins, e->plan.tiles, (double*)(e->ws + e->lay.partials));
+                           (const double2*)(e->ws + e->lay.tables), e->cfg.n_chains, e->cfg.n_bins, e->plan.scan.tiles, (double*)(e->ws + e->lay.partials));
     else
         hipLaunchKernelGGL((lr_pairscan_kernel<H, false>), grid, dim3(256), 0, stream, pk, e->n8,
-                           (const double2*)(e->ws + e->lay.tables), e->cfg.n_chains, e->cfg.n_bins, e->plan.tiles, (double*)(e->ws + e->lay.partials));
+                           (const double2*)(e->ws + e->lay.tables), e->cfg.n_chains, e->cfg.n_bins, e->plan.scan.tiles, (double*)(e->ws + e->lay.partials));
     return (int)hipGetLastError();
 }
 
 static int lr_enqueue_scan_range(const lr_engine* e, int base, int count, hipStream_t stream) {
     if (e->packed_scan) return lr_launch_packscan(e, base, count, stream);      // (never pipelined: a partition's chains in one launch)
-    if (e->plan.unit == LR_TAB_PAIRGEN || (e->persistent && (e->cfg.model == LR_MODEL_KEIDING_DEAD || e->plan.H == LR_H_WIDE))) {
+    if (e->plan.pair_only) {
         // pair-general tables / the extant block of model 3: the launch-based twin of the persistent scan, all chains at once
         if (base != 0 || count != e->cfg.n_chains) return LR_ERR_STATE;
-        switch (e->plan.H) {
+        switch (e->plan.scan.H) {
             case 40: return lr_launch_pairscan<40>(e, stream);
             case 72: return lr_launch_pairscan<72>(e, stream);
             case 136: return lr_launch_pairscan<136>(e, stream);
@@ -1503,9 +1071,9 @@ static int lr_enqueue_scan_range(const lr_engine* e, int base, int count, hipStr
             default: return lr_launch_pairscan<LR_H_WIDE>(e, stream);
         }
     }
-    return lr_launch_scan(e->plan, e->ts, e->te, e->cfg.n_lineages, e->cfg.t0, e->cfg.n_bins, e->cfg.end_time,
-                          (const double2*)(e->ws + e->lay.tables) + (size_t)base * e->plan.tab_stride, count,
-                          (double*)(e->ws + e->lay.partials) + (size_t)base * lr_tile_stride(e->plan.tiles), lr_tile_stride(e->plan.tiles), stream);
+    return lr_launch_scan(e->plan.scan, e->ts, e->te, e->cfg.n_lineages, e->cfg.t0, e->cfg.n_bins, e->cfg.end_time,
+                          (const double2*)(e->ws + e->lay.tables) + (size_t)base * e->plan.scan.tab_stride, count,
+                          (double*)(e->ws + e->lay.partials) + (size_t)base * lr_tile_stride(e->plan.scan.tiles), lr_tile_stride(e->plan.scan.tiles), stream);
 }
 static int lr_enqueue_scan(const lr_engine* e, hipStream_t stream) {
     return lr_enqueue_scan_range(e, 0, e->cfg.n_chains, stream);
@@ -1538,13 +1106,13 @@ static void lr_prepare_constants(const lr_engine* e, const lr_step_args& a, hipS
         (void)hipMemsetAsync(e->ws + e->lay.status, 0, 256, stream);
     }
     // ... and nothing carried over from the launches before it (four-chain kernel)
-    if (e->lay.persistent == 2) (void)hipMemsetAsync(e->ws + e->lay.xchg, 0, (size_t)((e->cfg.n_chains + 3) / 4) * LR_P4_CARRY_BYTES, stream);
+    if (e->plan.family == 2) (void)hipMemsetAsync(e->ws + e->lay.xchg, 0, (size_t)((e->cfg.n_chains + 3) / 4) * LR_P4_CARRY_BYTES, stream);
     hipLaunchKernelGGL(lr_log_br_kernel, dim3((e->cfg.n_bins + 127) / 128), dim3(128), 0, stream, e->br_length,
                        e->cfg.n_bins, (double*)(e->ws + e->lay.bin_consts));
     if (e->cfg.sampler == 1)
         hipLaunchKernelGGL(lr_dd_consts_kernel, dim3(1), dim3(LR_WAVE), 0, stream, e->br_length, e->cfg.n_bins,
                            (double*)(e->ws + e->lay.bin_consts) + e->cfg.n_bins);
-    if (e->persistent) {
+    if (e->plan.family) {
         static_assert(sizeof(lr_step_args) <= 1024, "args blob too small");
         hipLaunchKernelGGL(lr_store_args_kernel, dim3(1), dim3(64), 0, stream, a, (lr_step_args*)(e->ws + e->lay.args_blob));
     }
@@ -1554,12 +1122,12 @@ static void lr_prepare_constants(const lr_engine* e, const lr_step_args& a, hipS
 // birth bin) falls back to the scan of ts / te - same plan, same partials, same results to rounding
 // (general times have no such twin: their tables are the pair-general ones - the error is the caller's
 static int lr_pack_for_scan(lr_engine* e, hipStream_t stream) {
-    if (!e->lay.packed_scan) return LR_OK;
+    if (!e->plan.packed_scan) return LR_OK;
     const int rc = lr_pack_lineages(e, stream);
     e->packed_scan = rc == LR_OK;
     // (... nor has model 3 on these tables: the extant block is reached through the packed slots only)
     // (... nor the H = 520 class: the scans of ts / te are instantiated up to H = 264)
-    return (rc != LR_OK && (e->plan.unit == LR_TAB_PAIRGEN || e->cfg.model == LR_MODEL_KEIDING_DEAD || e->plan.H == LR_H_WIDE)) ? rc : LR_OK;
+    return (rc != LR_OK && e->plan.pair_only) ? rc : LR_OK;
 }
 
 extern "C" int lr_mcmc_restore(lr_engine* e, void* stream_) {
@@ -1569,7 +1137,7 @@ extern "C" int lr_mcmc_restore(lr_engine* e, void* stream_) {
     lr_prepare_constants(e, a, stream, true);
     int rc = (int)hipGetLastError();
     if (rc) return rc;
-    if (e->persistent) rc = lr_pack_lineages(e, stream);
+    if (e->plan.family) rc = lr_pack_lineages(e, stream);
     if (rc) return rc;
     rc = lr_pack_for_scan(e, stream);
     if (rc) return rc;
@@ -1586,7 +1154,7 @@ extern "C" int lr_mcmc_init(lr_engine* e, const double* L, const double* M, cons
     hipStream_t stream = (hipStream_t)stream_;
     const lr_step_args a = lr_make_args(e);
     lr_prepare_constants(e, a, stream, false);
-    if (e->persistent) {
+    if (e->plan.family) {
         const int rcp = lr_pack_lineages(e, stream);
         if (rcp) return rcp;
     }
@@ -1627,7 +1195,7 @@ template <int CB, int H, bool UNIT>
 static int lr_launch_fused(const lr_engine* e, const lr_step_args& a, const lr_fused_args& f, hipStream_t stream) {
     const int groups = (f.scan_n + CB - 1) / CB;
     const int blocks = f.step_blocks + groups * f.tiles;
-    const size_t lds_bytes = e->plan.lds_bytes > (int)(LR_STEP_WAVES * sizeof(lr_seg_scratch)) ? (size_t)e->plan.lds_bytes : LR_STEP_WAVES * sizeof(lr_seg_scratch);
+    const size_t lds_bytes = e->plan.scan.lds_bytes > (int)(LR_STEP_WAVES * sizeof(lr_seg_scratch)) ? (size_t)e->plan.scan.lds_bytes : LR_STEP_WAVES * sizeof(lr_seg_scratch);
     hipLaunchKernelGGL((lr_fused_iter_kernel<CB, H, UNIT>), dim3(blocks), dim3(LR_SCAN_THREADS), lds_bytes,
                        stream, a, f);
     return (int)hipGetLastError();
@@ -1636,14 +1204,14 @@ static int lr_launch_fused(const lr_engine* e, const lr_step_args& a, const lr_f
 // instantiated shapes: see lr_fused_supported()
 template <int H>
 static int lr_launch_fused_h(const lr_engine* e, const lr_step_args& a, const lr_fused_args& f, hipStream_t stream) {
-    if (e->plan.unit) {
-        switch (e->plan.cb) {
+    if (e->plan.scan.unit) {
+        switch (e->plan.scan.cb) {
             case 16: return lr_launch_fused<16, H, true>(e, a, f, stream);
             case 8: return lr_launch_fused<8, H, true>(e, a, f, stream);
             default: return LR_ERR_SIZE;
         }
     }
-    switch (e->plan.cb) {
+    switch (e->plan.scan.cb) {
         case 8: return lr_launch_fused<8, H, false>(e, a, f, stream);
         case 4: return lr_launch_fused<4, H, false>(e, a, f, stream);
         default: return LR_ERR_SIZE;
@@ -1654,11 +1222,11 @@ static int lr_launch_fused_h(const lr_engine* e, const lr_step_args& a, const lr
 static int lr_enqueue_fused(const lr_engine* e, const lr_step_args& a, int scan_base, int scan_n, int step_base,
                             int step_n, hipStream_t stream) {
     lr_fused_args f;
-    f.ts = e->ts, f.te = e->te, f.n = e->cfg.n_lineages, f.chunk = e->plan.chunk, f.t0 = e->cfg.t0;
-    f.n_bins = e->cfg.n_bins, f.tiles = e->plan.tiles;
+    f.ts = e->ts, f.te = e->te, f.n = e->cfg.n_lineages, f.chunk = e->plan.scan.chunk, f.t0 = e->cfg.t0;
+    f.n_bins = e->cfg.n_bins, f.tiles = e->plan.scan.tiles;
     f.scan_base = scan_base, f.scan_n = scan_n, f.step_base = step_base, f.step_n = step_n;
     f.step_blocks = (step_n + LR_STEP_WAVES - 1) / LR_STEP_WAVES;
-    switch (e->plan.H) {
+    switch (e->plan.scan.H) {
         case 40: return lr_launch_fused_h<40>(e, a, f, stream);
         case 72: return lr_launch_fused_h<72>(e, a, f, stream);
         case 136: return lr_launch_fused_h<136>(e, a, f, stream);
@@ -1742,20 +1310,20 @@ extern "C" int lr_mcmc_steps(lr_engine* e, int64_t n_iters, void* stream_) {
     if (n_iters == 0) return LR_OK;
     hipStream_t stream = (hipStream_t)stream_;
     const lr_step_args a = lr_make_args(e);
-    if (e->persistent) {
+    if (e->plan.family) {
         const uint4* idx8 = (const uint4*)(e->ws + e->lay.lineage_idx);
-        const bool general = e->plan.unit == LR_TAB_PAIRGEN;
+        const bool general = e->plan.scan.unit == LR_TAB_PAIRGEN;
         lr_packed_lineages pk;
         pk.idx8 = idx8, pk.frac = general ? (const uint4*)(e->ws + e->lay.lineage_frac) : nullptr, pk.fstride = e->n8_alloc;
         if (e->n8 <= 0) return LR_ERR_STATE;
         const lr_step_args* ap = (const lr_step_args*)(e->ws + e->lay.args_blob);
         const int blocks = (e->cfg.n_chains + 1) / 2;
-        const bool p4 = e->lay.persistent == 2;
+        const bool p4 = e->plan.family == 2;
         const bool param = e->cfg.sampler != 0;
         static const int prio = lr_env_int("LR_PERSIST_PRIO", 12);   // clock bits per priority slice, 0 = off
         // one block per CU at most: give it the whole CU (16 waves on the one pair)
-        const bool wide = e->lay.reserved1 == 1024;   // (short scans keep 512: the 16-wave barrier costs more than it buys)
-        if (e->lay.persistent == 3) return lr_launch_spec(e, a, pk, n_iters, stream);
+        const bool wide = e->plan.threads == 1024;   // (short scans keep 512: the 16-wave barrier costs more than it buys)
+        if (e->plan.family == 3) return lr_launch_spec(e, a, pk, n_iters, stream);
         for (int64_t done = 0; done < n_iters;) {
             const int64_t n = (n_iters - done > 4096) ? 4096 : n_iters - done;   // keep single launches short
         static const int carry_env = lr_env_int("LR_P4_CARRY", 1);   // 0: every launch scans pair 0 again (A/B runs)
@@ -1784,7 +1352,7 @@ extern "C" int lr_mcmc_steps(lr_engine* e, int64_t n_iters, void* stream_) {
     } else {                                                                                                                  \
         hipLaunchKernelGGL((lr_persist_kernel<HH, 512>), dim3(blocks), dim3(512), 0, stream, ap, idx8, e->n8, e->p4, (long long)n, prio); \
     }
-            switch (e->plan.H) {
+            switch (e->plan.scan.H) {
                 case 40: LR_P_LAUNCH(40); break;
                 case 72: LR_P_LAUNCH(72); break;
                 case 136: LR_P_LAUNCH(136); break;
@@ -1799,11 +1367,11 @@ extern "C" int lr_mcmc_steps(lr_engine* e, int64_t n_iters, void* stream_) {
         return LR_OK;
     }
     if (e->streaming) return lr_launch_stream(e, a, n_iters, false, stream);
-    if (e->n_parts == 1) return lr_run_part(e, a, e->part[0], n_iters, stream);
+    if (e->plan.n_parts == 1) return lr_run_part(e, a, e->part[0], n_iters, stream);
     // fork: every partition's stream waits for the caller's stream, runs its own sequence, and is joined back
     hipError_t he = hipEventRecord(e->fork, stream);
     if (he != hipSuccess) return (int)he;
-    for (int p = 0; p < e->n_parts; ++p) {
+    for (int p = 0; p < e->plan.n_parts; ++p) {
         lr_part& q = e->part[p];
         he = hipStreamWaitEvent(q.stream, e->fork, 0);
         if (he != hipSuccess) return (int)he;
@@ -1867,7 +1435,7 @@ extern "C" int lr_mcmc_warnings(lr_engine* e, int32_t* warnings, void* stream_) 
 // configuration word of the four-chain kernel an engine runs (0 = the generic instantiation, or another kernel)
 extern "C" int lr_mcmc_p4_config(const lr_engine* e, int32_t* word) {
     if (!e || !word) return LR_ERR_NULL;
-    *word = (e->persistent && e->lay.persistent == 2 && e->p4_help) ? e->p4_cfg : LR_P4_CFG_GENERIC;
+    *word = (e->plan.family == 2 && e->p4_help) ? e->p4_cfg : LR_P4_CFG_GENERIC;
     return LR_OK;
 }
 
@@ -1876,7 +1444,7 @@ extern "C" int lr_mcmc_p4_config(const lr_engine* e, int32_t* word) {
 // lane, packed groups, the helpers' trips
 extern "C" int lr_mcmc_p4_resident(const lr_engine* e, int32_t* out) {
     if (!e || !out) return LR_ERR_NULL;
-    const bool help = e->persistent && e->lay.persistent == 2 && e->p4_help;
+    const bool help = e->plan.family == 2 && e->p4_help;
     const long long h = help ? e->p4.help_trips : 0;
     const long long k_tot = (e->n8 - h * 128 + 767) / 768;        // trips of the first scanner wave: the most any wave makes
     const bool on = help && e->p4_resident && LR_P4_NR > 0;
@@ -1892,35 +1460,35 @@ extern "C" int lr_mcmc_p4_resident(const lr_engine* e, int32_t* out) {
 extern "C" int lr_mcmc_describe(const lr_engine* e, char* buf, int32_t n) {
     if (!e || !buf) return LR_ERR_NULL;
     if (n < 64) return LR_ERR_SIZE;
-    if (e->persistent) {
-        const char* gen = e->plan.unit == LR_TAB_PAIRGEN ? "true" : "false";
-        if (e->lay.persistent == 3)
-            snprintf(buf, (size_t)n, "lr_spec_kernel<%d, %d, %s, %s, %d>", e->plan.H, e->lay.reserved1, e->cfg.sampler == 0 ? "true" : "false", gen,
+    if (e->plan.family) {
+        const char* gen = e->plan.scan.unit == LR_TAB_PAIRGEN ? "true" : "false";
+        if (e->plan.family == 3)
+            snprintf(buf, (size_t)n, "lr_spec_kernel<%d, %d, %s, %s, %d>", e->plan.scan.H, e->plan.threads, e->cfg.sampler == 0 ? "true" : "false", gen,
                      lr_spec_mode(e));
-        else if (e->lay.persistent == 2)
-            snprintf(buf, (size_t)n, "lr_persist4_kernel<%d, %s, %s, %s>", e->plan.H, gen, e->cfg.sampler != 0 ? "true" : "false",
+        else if (e->plan.family == 2)
+            snprintf(buf, (size_t)n, "lr_persist4_kernel<%d, %s, %s, %s>", e->plan.scan.H, gen, e->cfg.sampler != 0 ? "true" : "false",
                      e->p4_help ? "true" : "false");
-        else snprintf(buf, (size_t)n, "lr_persist_kernel<%d, %d>", e->plan.H, e->lay.reserved1);
+        else snprintf(buf, (size_t)n, "lr_persist_kernel<%d, %d>", e->plan.scan.H, e->plan.threads);
     } else if (e->packed_scan) {
-        snprintf(buf, (size_t)n, "lr_packscan_kernel<%d, %d, %s>", lr_packscan_pairs(e->plan, e->cfg.n_chains), e->plan.H,
-                 e->plan.unit == LR_TAB_PAIRGEN ? "true" : "false");
+        snprintf(buf, (size_t)n, "lr_packscan_kernel<%d, %d, %s>", lr_packscan_pairs(e->plan.scan, e->cfg.n_chains), e->plan.scan.H,
+                 e->plan.scan.unit == LR_TAB_PAIRGEN ? "true" : "false");
     } else if (e->streaming) {
-        snprintf(buf, (size_t)n, "lr_stream_kernel<%d, %d, %s>", e->plan.cb, e->plan.H, e->plan.unit ? "true" : "false");
+        snprintf(buf, (size_t)n, "lr_stream_kernel<%d, %d, %s>", e->plan.scan.cb, e->plan.scan.H, e->plan.scan.unit ? "true" : "false");
     } else if (e->part[0].pipelined) {
-        snprintf(buf, (size_t)n, "lr_fused_iter_kernel<%d, %d, %s>", e->plan.cb, e->plan.H, e->plan.unit ? "true" : "false");
-    } else if (e->plan.fast && !e->plan.unit && e->plan.cb == 16) {
-        snprintf(buf, (size_t)n, "lr_scan_wide_kernel<%d>", e->plan.H);
-    } else if (e->plan.fast) {
-        snprintf(buf, (size_t)n, "%s<%d, %d>", e->plan.unit ? "lr_scan_unit_kernel" : "lr_scan_fast_kernel", e->plan.cb, e->plan.H);
+        snprintf(buf, (size_t)n, "lr_fused_iter_kernel<%d, %d, %s>", e->plan.scan.cb, e->plan.scan.H, e->plan.scan.unit ? "true" : "false");
+    } else if (e->plan.scan.fast && !e->plan.scan.unit && e->plan.scan.cb == 16) {
+        snprintf(buf, (size_t)n, "lr_scan_wide_kernel<%d>", e->plan.scan.H);
+    } else if (e->plan.scan.fast) {
+        snprintf(buf, (size_t)n, "%s<%d, %d>", e->plan.scan.unit ? "lr_scan_unit_kernel" : "lr_scan_fast_kernel", e->plan.scan.cb, e->plan.scan.H);
     } else {
-        snprintf(buf, (size_t)n, "lr_scan_kernel<%d>", e->plan.cb);
+        snprintf(buf, (size_t)n, "lr_scan_kernel<%d>", e->plan.scan.cb);
     }
     return LR_OK;
 }
 
 extern "C" int lr_mcmc_destroy(lr_engine* e) {
     if (!e) return LR_ERR_NULL;
-    for (int p = 0; p < e->n_parts; ++p) {
+    for (int p = 0; p < e->plan.n_parts; ++p) {
         lr_part& q = e->part[p];
         if (q.graph_exec) (void)hipGraphExecDestroy(q.graph_exec);
         if (q.done) (void)hipEventDestroy(q.done);

@@ -40,11 +40,6 @@
 
 #include "lr_engine.h"
 
-static int lr_env_int_pack(const char* name, int dflt) {
-    const char* v = getenv(name);
-    return v ? atoi(v) : dflt;
-}
-
 __device__ __forceinline__ int lr_birth_index(double s, double t0, int n_bins) {
     return min(max(__double2int_rz(floor(s) - t0), -1), n_bins) + 1;
 }
@@ -210,7 +205,7 @@ static void lr_set_shares(lr_engine* e) {
     // serves its oldest wave first and SIMDs 0, 1 also host the stepper waves, hence the shape.  Kept as fractions of
     // the trip count for other inputs; short scans (bound by the chain step) stay equal.
     static const char* env = getenv("LR_P4_SHARES");       // "d2,d4,d6,d8,d10,d12,d14" for 14 trips
-    static const int env2 = lr_env_int_pack("LR_P2_SHARE", 0);   // two-chain kernel (no gain measured: off)
+    static const int env2 = lr_env_int("LR_P2_SHARE", 0);   // two-chain kernel (no gain measured: off)
     for (int j = 0; j < 16; ++j) e->p4.delta[j] = 0;
     e->p4.help_trips = 0;
     e->p4_help = lr_p4_help_choice(e);
@@ -222,7 +217,7 @@ static void lr_set_shares(lr_engine* e) {
         // With t trips per scanner lane behind that share (groups = 128 h + 768 t) the two sides end together at about
         // h = t - 3.5; more than five never paid - the helpers scan with plain loads, one group in flight per lane
         // (scratch/exp_help_trips.py: 60k lineages 2, cfg4 5, 300k and 1M 5).  LR_P4_HELP_TRIPS overrides it.
-        static const int env_t = lr_env_int_pack("LR_P4_HELP_TRIPS", -1);
+        static const int env_t = lr_env_int("LR_P4_HELP_TRIPS", -1);
         const double t = ((double)e->n8 + 512.0) / 896.0;
         int h = (int)lrint(t - 3.5);
         h = h < 0 ? 0 : (h > 5 ? 5 : h);
@@ -262,7 +257,7 @@ static void lr_set_shares(lr_engine* e) {
     } else {
         // two-chain kernel: 8 waves, two per SIMD (16 in its wide form, four per SIMD: the oldest-first pattern of the
         // four-chain kernel - waves 0..3 / 4..7 take trips from 12..15 / 8..11, per 12 trips)
-        const bool wide2 = e->lay.reserved1 == 1024;
+        const bool wide2 = e->plan.threads == 1024;
         e->p4.n_slots = wide2 ? 16 : 8;
         const int k_tot = (int)((e->n8 + e->p4.n_slots * 64 - 1) / (e->p4.n_slots * 64));
         int d = (k_tot >= 12) ? (int)lrint((double)env2 * k_tot / 24.0) : 0;
@@ -293,7 +288,7 @@ static void lr_set_shares(lr_engine* e) {
 int lr_pack_lineages(lr_engine* e, hipStream_t stream) {
     const long long n = e->cfg.n_lineages;
     if (n >= (1ll << 31)) return LR_ERR_SIZE;                         // lineage numbers are scanned as int32
-    const bool general = e->plan.unit == LR_TAB_PAIRGEN;
+    const bool general = e->plan.scan.unit == LR_TAB_PAIRGEN;
     const int extant_block = e->cfg.model == LR_MODEL_KEIDING_DEAD ? 1 : 0;
     char* tmp = e->ws + e->lay.pack_tmp;
     const long long arr = lr_align_up64(n * 4, 256);
@@ -343,7 +338,7 @@ int lr_pack_lineages(lr_engine* e, hipStream_t stream) {
     const long long share_base = (e->lay.persistent == 2 && e->p4_help) ? (long long)e->p4.help_trips * 128 : 0;
     const int k_tot = (int)((e->n8 - share_base + e->p4.n_slots * 64 - 1) / (e->p4.n_slots * 64));
     // (an all-zero group of the spare: birth entry 0 x count 0 and seven gathers of S[0] = 0 - contribution 0)
-    hipLaunchKernelGGL(lr_pack_slots_kernel, grid, blk, 0, stream, e->ts, e->te, n, e->cfg.t0, e->cfg.n_bins, e->plan.H,
+    hipLaunchKernelGGL(lr_pack_slots_kernel, grid, blk, 0, stream, e->ts, e->te, n, e->cfg.t0, e->cfg.n_bins, e->plan.scan.H,
                        (const int*)run_start, (const int*)stretch_start, (const int*)head_incl, (const int*)group_incl,
                        any ? 1 : 0, k_tot, share_base, e->p4, (unsigned short*)(e->ws + e->lay.lineage_idx), extant_block, e->cfg.end_time,
                        general ? (unsigned int*)(e->ws + e->lay.lineage_frac) : nullptr, (long long)e->n8_alloc);

@@ -15,7 +15,7 @@
 // 16 chains x 1e7 / 3e7 / 1e8 lineages: 16.5 / 27 / 54-59 us per iteration against 35.5 / 95 / 285 with the scan of ts / te
 // (profiles/r05_packed_scan.txt); general lineage times in the pair-general form (GENERAL below).
 // Tile partials as everywhere: partials[chain * lr_tile_stride(tiles) + tile], summed by lr_chain_step_kernel.
-// The planner (lr_mcmc.hip: lr_packscan_planned, lr_packed_mode) takes it wherever the launches run with few chains or
+// The planner (lr_plan.hip: lr_packscan_planned, lr_packed_mode) takes it wherever the launches run with few chains or
 // long passes, never pipelined; long scans run in two partitions of the chains on their own streams.
 #include <cstdlib>
 
@@ -178,7 +178,7 @@ bool lr_packscan_eligible(const lr_mcmc_config* cfg, const lr_scan_plan& p) {
     if (cfg->engine_mode != 7 && (!env || cfg->engine_mode != 0)) return false;     // (7 = asked for; auto unless switched off)
     if ((p.unit != LR_TAB_UNIT && p.unit != LR_TAB_PAIRGEN) || !p.fast || p.cb < 2) return false;    // pair tables
     if (p.H != 40 && p.H != 72 && p.H != 136 && p.H != 264 && p.H != LR_H_WIDE) return false;
-    // the packing holds lineage indices as int32 and the groups are addressed by 32-bit offsets (as lr_persist_eligible)
+    // the packing holds lineage indices as int32 and the groups are addressed by 32-bit offsets (as lr_persist_family)
     if (cfg->n_lineages >= (1ll << 31) - 1 || lr_groups_alloc(cfg->n_lineages) * 16 >= (1ll << 32)) return false;
     return true;
 }
@@ -217,24 +217,24 @@ static int lr_packscan_launch(const lr_engine* e, int base, int count, hipStream
         if (he != hipSuccess) return (int)he;
     }
     const int n_pairs = (base + count + 1) / 2 - base / 2;
-    const dim3 grid(e->plan.tiles, (n_pairs + PAIRS - 1) / PAIRS);
+    const dim3 grid(e->plan.scan.tiles, (n_pairs + PAIRS - 1) / PAIRS);
     hipLaunchKernelGGL((lr_packscan_kernel<PAIRS, H, GENERAL>), grid, dim3(LR_PACKSCAN_THREADS), lds, stream,
                        (const uint4*)(e->ws + e->lay.lineage_idx), (const uint4*)(e->ws + e->lay.lineage_frac), (long long)e->n8_alloc, e->n8,
-                       (const double2*)(e->ws + e->lay.tables), base, base + count, e->cfg.n_bins, e->plan.tiles,
+                       (const double2*)(e->ws + e->lay.tables), base, base + count, e->cfg.n_bins, e->plan.scan.tiles,
                        (double*)(e->ws + e->lay.partials));
     return (int)hipGetLastError();
 }
 
 template <int H>
 static int lr_packscan_launch_h(const lr_engine* e, int base, int count, hipStream_t stream) {
-    if (e->plan.unit == LR_TAB_PAIRGEN) {
-        switch (lr_packscan_pairs(e->plan, e->cfg.n_chains)) {
+    if (e->plan.scan.unit == LR_TAB_PAIRGEN) {
+        switch (lr_packscan_pairs(e->plan.scan, e->cfg.n_chains)) {
             case 4: return lr_packscan_launch<4, H, true>(e, base, count, stream);
             case 2: return lr_packscan_launch<2, H, true>(e, base, count, stream);
             default: return lr_packscan_launch<1, H, true>(e, base, count, stream);
         }
     }
-    switch (lr_packscan_pairs(e->plan, e->cfg.n_chains)) {
+    switch (lr_packscan_pairs(e->plan.scan, e->cfg.n_chains)) {
         case 8: return lr_packscan_launch<8, H, false>(e, base, count, stream);
         case 4: return lr_packscan_launch<4, H, false>(e, base, count, stream);
         case 2: return lr_packscan_launch<2, H, false>(e, base, count, stream);
@@ -245,7 +245,7 @@ static int lr_packscan_launch_h(const lr_engine* e, int base, int count, hipStre
 // one pass of the packed lineages for the chains [base, base + count) (base even: a partition of the engine)
 int lr_launch_packscan(const lr_engine* e, int base, int count, hipStream_t stream) {
     if (e->n8 <= 0 || (base & 1) || count < 1) return LR_ERR_STATE;
-    switch (e->plan.H) {
+    switch (e->plan.scan.H) {
         case 40: return lr_packscan_launch_h<40>(e, base, count, stream);
         case 72: return lr_packscan_launch_h<72>(e, base, count, stream);
         case 136: return lr_packscan_launch_h<136>(e, base, count, stream);

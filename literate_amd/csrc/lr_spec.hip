@@ -8,7 +8,7 @@ int lr_launch_spec(lr_engine* e, const lr_step_args& a, const lr_packed_lineages
     const int cpb = e->lay.spec_chains_per_team == 1 ? 1 : 2;
     const int mode = lr_spec_mode(e);
     const int blocks = (e->cfg.n_chains + cpb - 1) / cpb;          // teams
-    const bool general = e->plan.unit == LR_TAB_PAIRGEN;
+    const bool general = e->plan.scan.unit == LR_TAB_PAIRGEN;
             lr_spec_args x;
             x.xchg = (unsigned long long*)(e->ws + e->lay.xchg);
             x.status = (unsigned int*)(e->ws + e->lay.status);
@@ -54,16 +54,16 @@ int lr_launch_spec(lr_engine* e, const lr_step_args& a, const lr_packed_lineages
         else if (mode == 1) LR_SPEC_LAUNCH_M(HH, GG, false, 1);                        \
         else LR_SPEC_LAUNCH_M(HH, GG, false, 0);                                       \
     }
-                // (general times: H = 264 is never planned for this kernel, see lr_persist_variant)
+                // (general times: H = 264 is never planned for this kernel, see lr_persist_family in lr_plan.hip)
                 if (general) {
-                    switch (e->plan.H) {
+                    switch (e->plan.scan.H) {
                         case 40: LR_SPEC_LAUNCH(40, true); break;
                         case 72: LR_SPEC_LAUNCH(72, true); break;
                         case 136: LR_SPEC_LAUNCH(136, true); break;
                         default: return LR_ERR_SIZE;
                     }
                 } else {
-                    switch (e->plan.H) {
+                    switch (e->plan.scan.H) {
                         case 40: LR_SPEC_LAUNCH(40, false); break;
                         case 72: LR_SPEC_LAUNCH(72, false); break;
                         case 136: LR_SPEC_LAUNCH(136, false); break;

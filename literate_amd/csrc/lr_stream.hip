@@ -418,14 +418,14 @@ static int lr_stream_launch_one(const lr_engine* e, const lr_step_args& a, const
 template <int H>
 static int lr_stream_launch_h(const lr_engine* e, const lr_step_args& a, const lr_stream_args& f, int grid, size_t lds_bytes, bool query,
                               hipStream_t stream) {
-    if (e->plan.unit) {
-        switch (e->plan.cb) {
+    if (e->plan.scan.unit) {
+        switch (e->plan.scan.cb) {
             case 16: return lr_stream_launch_one<16, H, true>(e, a, f, grid, lds_bytes, query, stream);
             case 8: return lr_stream_launch_one<8, H, true>(e, a, f, grid, lds_bytes, query, stream);
             default: return LR_ERR_SIZE;
         }
     }
-    switch (e->plan.cb) {
+    switch (e->plan.scan.cb) {
         case 8: return lr_stream_launch_one<8, H, false>(e, a, f, grid, lds_bytes, query, stream);
         case 4: return lr_stream_launch_one<4, H, false>(e, a, f, grid, lds_bytes, query, stream);
         default: return LR_ERR_SIZE;
@@ -435,14 +435,14 @@ static int lr_stream_launch_h(const lr_engine* e, const lr_step_args& a, const l
 // query = true: only asks whether the grid fits the device in use (LR_OK / LR_ERR_STATE)
 int lr_launch_stream(lr_engine* e, const lr_step_args& a, int64_t n_iters, bool query, hipStream_t stream) {
     lr_stream_args f;
-    f.ts = e->ts, f.te = e->te, f.n = e->cfg.n_lineages, f.chunk = e->plan.chunk, f.t0 = e->cfg.t0;
-    f.n_bins = e->cfg.n_bins, f.tiles = e->plan.tiles, f.groups = e->plan.groups;
+    f.ts = e->ts, f.te = e->te, f.n = e->cfg.n_lineages, f.chunk = e->plan.scan.chunk, f.t0 = e->cfg.t0;
+    f.n_bins = e->cfg.n_bins, f.tiles = e->plan.scan.tiles, f.groups = e->plan.scan.groups;
     f.step_blocks = lr_stream_step_blocks(e->cfg.n_chains);
     f.sync = (lr_stream_sync*)(e->ws + e->lay.xchg);
     f.tables2 = (double2*)(e->ws + e->lay.xchg + LR_STREAM_SYNC_BYTES);
     f.status = (unsigned int*)(e->ws + e->lay.status);
     const int grid = f.step_blocks + f.tiles * f.groups;
-    const size_t lds_bytes = lr_stream_lds_bytes(e->plan);
+    const size_t lds_bytes = lr_stream_lds_bytes(e->plan.scan);
     for (int64_t done = 0; done < n_iters || query;) {
         const int64_t n = (n_iters - done > 4096) ? 4096 : n_iters - done;   // keep single launches short
         f.n_iters = n;
@@ -452,7 +452,7 @@ int lr_launch_stream(lr_engine* e, const lr_step_args& a, int64_t n_iters, bool 
             if (he != hipSuccess) return (int)he;
         }
         int rc;
-        switch (e->plan.H) {
+        switch (e->plan.scan.H) {
             case 40: rc = lr_stream_launch_h<40>(e, a, f, grid, lds_bytes, query, stream); break;
             case 72: rc = lr_stream_launch_h<72>(e, a, f, grid, lds_bytes, query, stream); break;
             case 136: rc = lr_stream_launch_h<136>(e, a, f, grid, lds_bytes, query, stream); break;

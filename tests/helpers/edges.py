@@ -1,6 +1,6 @@
 """The chain engine's kernel-choice map as the tests see it.
 
-The planner (csrc/lr_mcmc.hip: lr_plan_engine, lr_persist_variant, lr_packscan_planned; csrc/lr_loglik.hip:
+The planner (csrc/lr_plan.hip: lr_plan_engine, lr_persist_family, lr_packscan_planned; csrc/lr_loglik.hip:
 lr_plan_scan) picks one of five kernel families for a configuration, each compiled for a fixed set of table
 half-strides H.  A CELL is (family, H, general, param, extant):
 
@@ -89,7 +89,7 @@ def spec_max_h(general):
 
 
 def engine_runs(engine, model, sampler, unit, n_bins):
-    """Whether a FORCED engine runs the configuration as that engine (the mirror of lr_persist_variant /
+    """Whether a FORCED engine runs the configuration as that engine (the mirror of lr_persist_family /
     lr_packscan_eligible at 37 chains); the GPU tests assert the layout agrees."""
     h = table_class(model, n_bins)
     if sampler != 0 and n_bins > PARAM_MAX_BINS:
