@@ -38,7 +38,8 @@ int lr_ade_classes(const double* ts, const double* te, int64_t n, double t0, int
                    int64_t* out_dead /* [A, A] */, int64_t* out_cens /* [A] */, int64_t* out_totals /* [2] */, void* stream);
 
 /* lr_ade_profile: for each of the S rows of mu_bins [S, A] and each of the G shapes, c^ = argmax_c l(c) and l(c^).  dead [A, A]
- *   and cens [A] as lr_ade_classes writes them; of dead only the cells with jb + a < A and a count > 0 are classes.
+ *   and cens [A] as lr_ade_classes writes them; of dead only the cells with jb + a < A and a count > 0 are classes (a negative
+ *   count is read as 0).
  *   Draw s is FLAGGED iff some mu[s, b] is not finite or < 0, or mu[s, je] == 0 for a bin je that holds an observed death:
  *   out_flag[s] = 1 (else 0) and the rows out_ll[s, .], out_c[s, .] are NaN.  A shape that is not finite or <= 0: its column is
  *   NaN.  No observed death: out_c = 0, out_ll = 0.  No finite maximiser (the coefficient of -c, sum of dead H[jb][a] and
@@ -48,8 +49,9 @@ int lr_ade_classes(const double* ts, const double* te, int64_t n, double t0, int
  *   The sums are formed in an order that depends on the arguments' sizes alone and there are no floating-point atomics: a
  *   result is a function of (dead, cens, mu[s, .], shapes[g]) alone - the same bits from a second call, on dirty buffers,
  *   beside other draws or without them.
- *   workspace: lr_ade_profile_workspace_bytes (the class list, the numbers at risk, one table per draw); < 0 = the LR_ERR_*
- *   of the sizes.
+ *   workspace: lr_ade_profile_workspace_bytes (the tables lr_adej_prepare writes too - the class list and the numbers at risk
+ *   as a packed triangle, as doubles and as 32-bit integers - and one row of A sums per draw); < 0 = the LR_ERR_* of the
+ *   sizes.
  *   Errors before any launch, in this order: LR_ERR_NULL; LR_ERR_SIZE: S < 1, G < 1, n_bins < 1 or > LR_ADE_MAX_BINS, or
  *   S G >= 2^31; LR_ERR_WORKSPACE.                                                                                          */
 int64_t lr_ade_profile_workspace_bytes(int32_t n_bins, int32_t S, int32_t G);

@@ -50,7 +50,8 @@ extern "C" {
  * ---- The buffers ----------------------------------------------------------------------------------------------------------
  * workspace: lr_adej_workspace_bytes(n_bins) bytes (< 0: LR_ERR_SIZE), written by lr_adej_prepare and only read by the others:
  *   a header, the classes with a count in the table's own order (so every sum over them has one order), the bins that hold a
- *   death, and R as a packed triangle.  Integer arithmetic on the counts; from the data only.
+ *   death, and R as a packed triangle - the tables lr_ade_profile starts its own workspace with, written by the same two
+ *   kernels.  Integer arithmetic on the counts; from the data only.
  * state [n_chains, LR_ADEJ_STATE_W]: 0 K, 1 g, 2 rate_hp, 3 poi_hp, 4 log-likelihood, 5 log prior, 6 .. 10 proposals made per
  *   move kind, 11 .. 15 proposals accepted per move kind, 16 .. 47 the rates, 48 .. 80 the times; every unused slot (rates and
  *   times beyond K, 81 .. 95) is 0.

@@ -88,15 +88,31 @@ def arg_error(burnin, n_draws, model=2, pyrate_output=False, rm_first_bin=False)
         return "--ade takes a burn-in fraction in [0, 1)"
     if n_draws < 1:
         return "--ade_draws must be at least 1"
+    return shared_refusal("--ade", "trace", model, pyrate_output, rm_first_bin)
+
+
+def shared_refusal(flag, reads, model, pyrate_output, rm_first_bin):
+    """What --ade and --ade_joint both refuse (None when nothing): flag - the option's name, reads - where it takes the
+    times from ("trace", "run")."""
     if pyrate_output:
-        return "--ade reads the AD / TBP times of the trace; -pyrate_output flips them in the logs: not supported together"
+        return "%s reads the AD / TBP times of the %s; -pyrate_output flips them in the logs: not supported together" % (flag, reads)
     if rm_first_bin:
-        return ("--ade fits the age effect on every lineage of the data; under -rm_first_bin 1 the lineages of the removed bin "
-                "were born outside the window the model was fitted on: not supported together")
+        return ("%s fits the age effect on every lineage of the data; under -rm_first_bin 1 the lineages of the removed bin "
+                "were born outside the window the model was fitted on: not supported together" % flag)
     if model == 3:
-        return ("--ade censors the extant lineages; under -model_BDI 3 the death rates were fitted to the extinct lineages "
-                "only, so the extant ones were never in that likelihood: not supported together")
+        return ("%s censors the extant lineages; under -model_BDI 3 the death rates were fitted to the extinct lineages "
+                "only, so the extant ones were never in that likelihood: not supported together" % flag)
     return None
+
+
+def class_counts(dead, cens, totals):
+    """The count fields of a fit row (--ade's and --ade_joint's) from ade_classes' host arrays; a class is a cell with
+    jb + a < A and a count > 0, as the device reads the table."""
+    dead, cens, totals = (np.asarray(x) for x in (dead, cens, totals))
+    A = len(cens)
+    is_class = (dead > 0) & (np.add.outer(np.arange(A), np.arange(A)) < A)
+    return dict(lineages=int(totals[0] + totals[1]), lineages_used=int(totals[0]), lineages_unused=int(totals[1]),
+                deaths=int(dead[is_class].sum()), censored=int(cens.sum()), classes=int(is_class.sum()))
 
 
 def coarse_shapes():
@@ -195,9 +211,7 @@ def fit_rates(ts, te, t0, mu_bins, profile=None, draw_rows=None):
         scale = float(np.float64(c_hat) ** (-1.0 / k_hat))
     weight = cond.p.mean(axis=0)
     st = np.asarray(be.summary(np.stack([cond.shape_ml, cond.lr], axis=1)), dtype=np.float64)
-    fit = dict(draws=S, draws_flagged=S - n_k, lineages=int(tot[0] + tot[1]), lineages_used=int(tot[0]),
-               lineages_unused=int(tot[1]), bins=A, deaths=int(dead.sum()), censored=int(cens.sum()),
-               classes=int((dead > 0).sum()))
+    fit = dict(draws=S, draws_flagged=S - n_k, bins=A, **class_counts(dead, cens, tot))
     fit.update(mixture(cond.fine_shapes, weight))
     logf = np.log(cond.fine_shapes)
     fit["grid_step_over_se"] = float((logf[-1] - logf[0]) / (N_FINE - 1) / np.median(cond.se))

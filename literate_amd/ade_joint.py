@@ -25,6 +25,8 @@ from collections import namedtuple
 
 import numpy as np
 
+from . import ade
+
 MAX_BINS = 128                      # LR_ADEJ_MAX_BINS
 MOVES = ("mult", "shape", "add", "remove", "gibbs")
 FIT_INTS = ["chains", "iterations", "samples_kept", "lineages", "lineages_used", "lineages_unused", "bins", "deaths", "censored",
@@ -57,17 +59,10 @@ def arg_error(burnin, n_iter, s_freq, win, n_bins=None, model=2, pyrate_output=F
     n = (int(n_iter) + int(s_freq) - 1) // int(s_freq)
     if n - int(burnin * n) < 4:
         return "--ade_joint: %d iterations at one row per %d leave fewer than 4 samples after the burn-in" % (n_iter, s_freq)
-    if pyrate_output:
-        return "--ade_joint reads the AD / TBP times of the run; -pyrate_output flips them in the logs: not supported together"
-    if rm_first_bin:
-        return ("--ade_joint fits the age effect on every lineage of the data; under -rm_first_bin 1 the lineages of the removed "
-                "bin were born outside the window the model was fitted on: not supported together")
-    if model == 3:
-        return ("--ade_joint censors the extant lineages; under -model_BDI 3 the death rates were fitted to the extinct lineages "
-                "only, so the extant ones were never in that likelihood: not supported together")
-    if n_bins is not None and n_bins > MAX_BINS:
+    shared = ade.shared_refusal("--ade_joint", "run", model, pyrate_output, rm_first_bin)
+    if shared is None and n_bins is not None and n_bins > MAX_BINS:
         return too_many_bins(n_bins)
-    return None
+    return shared
 
 
 def too_many_bins(n_bins):
@@ -137,11 +132,7 @@ def run(ts, te, t0, n_bins, chains, n_iter, s_freq, seed, settings=None, burnin=
     data = ops.adej_prepare(dead, cens)
     rows, state = ops.adej_run(data, t0, chains, n_iter, s_freq, seed, settings)
     dead_h, cens_h, tot_h = dead.cpu().numpy(), cens.cpu().numpy(), tot.cpu().numpy()
-    A = int(n_bins)
-    is_class = (dead_h > 0) & (np.add.outer(np.arange(A), np.arange(A)) < A)
-    counts = {"lineages": int(tot_h.sum()), "lineages_used": int(tot_h[0]), "lineages_unused": int(tot_h[1]),
-              "deaths": int(dead_h[is_class].sum()), "censored": int(cens_h.sum()), "classes": int(is_class.sum())}
-    fit, rates, draws, kept = summarise(rows, state, t0, n_bins, n_iter, burnin, counts)
+    fit, rates, draws, kept = summarise(rows, state, t0, n_bins, n_iter, burnin, ade.class_counts(dead_h, cens_h, tot_h))
     return AdeJointResult(rows, state, dead_h, cens_h, tot_h, kept, fit, rates, draws)
 
 

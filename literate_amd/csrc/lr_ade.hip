@@ -6,8 +6,9 @@
 //                          in LDS (the [A, A] table too while it fits: A <= LR_ADE_LDS_BINS), flushed with 64-bit integer
 //                          atomics; above that the table's cells take the atomics directly.
 //   lr_ade_prep_kernel     one block: the classes with a count, in the table's own order (a ballot scan, so the list - and
-//                          with it every later sum - has one order), the bins that hold a death, the number of deaths
+//                          with it every later sum - has one order), the bins that hold a death, the header
 //   lr_ade_risk_kernel     R[jb][j] = cens[jb] + sum_{a > j} dead[jb][a]: the lineages of birth bin jb that live past age j
+//                          (these two write the tables of lr_ade_tables.h, for the joint sampler of lr_adej.hip as well)
 //   lr_ade_draw_kernel     one block per draw: its flag, and M_s[j] = sum_jb R[jb][j] mu[s, jb + j], added in the order of jb
 //   lr_ade_profile_kernel  one block per (draw, shape)
 //
@@ -24,8 +25,7 @@
 
 #include <hip/hip_runtime.h>
 
-#include "../../include/literate_hip_ade.h"
-#include "lr_internal.h"
+#include "lr_ade_tables.h"
 
 #define LR_ADE_THREADS 256
 #define LR_ADE_WAVES (LR_ADE_THREADS / 64)
@@ -37,8 +37,6 @@
 #define LR_ADE_PREP_THREADS 1024
 #define LR_ADE_REG_CLASSES 4                             /* classes a thread keeps in registers across the Newton steps */
 #define LR_ADE_MAX_STEPS 60
-#define LR_ADE_HDR_CLASSES 0
-#define LR_ADE_HDR_DEATHS 1
 
 // ------------------------------------------------------------------------------------------
 // device side
@@ -92,18 +90,21 @@ __global__ __launch_bounds__(LR_ADE_THREADS) void lr_ade_classes_kernel(
 }
 
 // one block.  The cells (jb, a) with jb + a < A and a count > 0, in the order of the table: cls_cell[p] = je | a << 16,
-// cls_n[p] = the count; death_bin[je] = 1 where a death was observed; hdr = {classes, deaths}
-__global__ __launch_bounds__(LR_ADE_PREP_THREADS) void lr_ade_prep_kernel(const long long* __restrict__ dead, int A,
+// cls_n[p] / cls_n32[p] = the count; death_bin[je] = 1 where a death was observed; hdr = {classes, deaths, FITS32}
+__global__ __launch_bounds__(LR_ADE_PREP_THREADS) void lr_ade_prep_kernel(const long long* __restrict__ dead,
+                                                                          const long long* __restrict__ cens, int A,
                                                                           int* __restrict__ cls_cell,
                                                                           double* __restrict__ cls_n,
+                                                                          int* __restrict__ cls_n32,
                                                                           int* __restrict__ death_bin,
                                                                           long long* __restrict__ hdr) {
     __shared__ int s_wave[LR_ADE_PREP_THREADS / 64];
     __shared__ int s_bin[LR_ADE_MAX_BINS];
     __shared__ unsigned long long s_deaths;
+    __shared__ unsigned long long s_most;                  // the largest number of lineages of one birth bin
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     for (int i = tid; i < A; i += LR_ADE_PREP_THREADS) s_bin[i] = 0;
-    if (tid == 0) s_deaths = 0ull;
+    if (tid == 0) s_deaths = 0ull, s_most = 0ull;
     __syncthreads();
     const int cells = A * A;
     int base_pos = 0;
@@ -130,6 +131,7 @@ __global__ __launch_bounds__(LR_ADE_PREP_THREADS) void lr_ade_prep_kernel(const 
             const int p = base_pos + before + __popcll(votes & ((1ull << lane) - 1ull));
             cls_cell[p] = (jb + a) | (a << 16);
             cls_n[p] = (double)v;
+            cls_n32[p] = (int)(v < INT_MAX ? v : INT_MAX);
             s_bin[jb + a] = 1;
             mine += (unsigned long long)v;
         }
@@ -137,20 +139,34 @@ __global__ __launch_bounds__(LR_ADE_PREP_THREADS) void lr_ade_prep_kernel(const 
         __syncthreads();
     }
     if (mine) atomicAdd(&s_deaths, mine);
+    // a birth bin's lineages: R[jb][0] plus its deaths at age 0, the largest number any R or class count can reach
+    for (int jb = tid; jb < A; jb += LR_ADE_PREP_THREADS) {
+        unsigned long long tot = (unsigned long long)(cens[jb] > 0 ? cens[jb] : 0);
+        for (int a = 0; a < A - jb; ++a) {
+            const long long v = dead[(size_t)jb * A + a];
+            tot += (unsigned long long)(v > 0 ? v : 0);
+        }
+        atomicMax(&s_most, tot);
+    }
     __syncthreads();
     for (int i = tid; i < A; i += LR_ADE_PREP_THREADS) death_bin[i] = s_bin[i];
-    if (tid == 0) hdr[LR_ADE_HDR_CLASSES] = base_pos, hdr[LR_ADE_HDR_DEATHS] = (long long)s_deaths;
+    if (tid == 0) {
+        hdr[LR_ADE_HDR_CLASSES] = base_pos, hdr[LR_ADE_HDR_DEATHS] = (long long)s_deaths;
+        hdr[LR_ADE_HDR_FITS32] = s_most < (unsigned long long)INT_MAX ? 1 : 0;
+    }
 }
 
-// R[jb * A + j], j = 0 .. A - jb - 1 (the rest of a row is never read)
+// R and R32, row jb by thread jb (a negative count is read as 0)
 __global__ __launch_bounds__(LR_ADE_THREADS) void lr_ade_risk_kernel(const long long* __restrict__ dead,
                                                                      const long long* __restrict__ cens, int A,
-                                                                     double* __restrict__ R) {
+                                                                     double* __restrict__ R, int* __restrict__ R32) {
     const int jb = blockIdx.x * LR_ADE_THREADS + threadIdx.x;
     if (jb >= A) return;
-    long long run = cens[jb];
+    long long run = cens[jb] > 0 ? cens[jb] : 0;
+    const int row = lr_ade_row(jb, A);
     for (int j = A - jb - 1; j >= 0; --j) {
-        R[(size_t)jb * A + j] = (double)run;
+        R[row + j] = (double)run;
+        R32[row + j] = (int)(run < INT_MAX ? run : INT_MAX);
         const long long v = dead[(size_t)jb * A + j];
         run += v > 0 ? v : 0;
     }
@@ -168,19 +184,20 @@ __global__ __launch_bounds__(LR_ADE_THREADS) void lr_ade_draw_kernel(const doubl
     for (int b = tid; b < A; b += LR_ADE_THREADS) {
         const double m = mu[b];
         s_mu[b] = m;
-        bad |= !(m >= 0.0) || !(m < __builtin_inf()) || (m == 0.0 && death_bin[b]);
+        bad |= lr_ade_bad_rate(m, death_bin, b);
     }
     bad = __syncthreads_or(bad);
     if (tid == 0) out_flag[s] = bad ? 1 : 0;
     if (bad) return;
     for (int j = tid; j < A; j += LR_ADE_THREADS) {
         double acc = 0.0;
-        for (int jb = 0; jb + j < A; ++jb) acc = fma(R[(size_t)jb * A + j], s_mu[jb + j], acc);
+        for (int jb = 0, row = 0; jb + j < A; row += A - jb, ++jb) acc = fma(R[row + j], s_mu[jb + j], acc);   // row = lr_ade_row(jb, A)
         M[(size_t)s * A + j] = acc;
     }
 }
 
 // (a, b) summed over the block, the same in every thread: lanes by shuffles, the waves one after the other
+// (not lr_adej_block_sum: that one adds the lanes in the order of a DPP scan, and the bits would differ)
 __device__ __forceinline__ void lr_ade_sum2(double& a, double& b, double* s_red) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
@@ -209,15 +226,11 @@ __device__ __forceinline__ void lr_ade_score(double n, double x, double& p, doub
     q += n * g * (1.0 - x / -expm1(-x));
 }
 
-// n log(1 - exp(-x))
-__device__ __forceinline__ double lr_ade_term(double n, double x) {
-    return n * (x < 0.6931471805599453 ? log(-expm1(-x)) : log1p(-exp(-x)));
-}
-
 __global__ __launch_bounds__(LR_ADE_THREADS) void lr_ade_profile_kernel(
-    const double* __restrict__ mu_bins, int A, const double* __restrict__ shapes, int G, const int* __restrict__ cls_cell,
-    const double* __restrict__ cls_n, const long long* __restrict__ hdr, const double* __restrict__ M,
-    const int* __restrict__ flag, double* __restrict__ out_ll, double* __restrict__ out_c) {
+    const double* __restrict__ mu_bins, int A, const double* __restrict__ shapes, int G, lr_ade_data d,
+    const double* __restrict__ M, const int* __restrict__ flag, double* __restrict__ out_ll, double* __restrict__ out_c) {
+    const int* __restrict__ cls_cell = d.cls_cell;
+    const double* __restrict__ cls_n = d.cls_n;
     __shared__ double s_mu[LR_ADE_MAX_BINS];
     __shared__ double s_w[LR_ADE_MAX_BINS];
     __shared__ double s_red[2 * LR_ADE_WAVES];
@@ -231,14 +244,15 @@ __global__ __launch_bounds__(LR_ADE_THREADS) void lr_ade_profile_kernel(
         if (tid == 0) out_ll[o] = nan, out_c[o] = nan;
         return;
     }
-    const double D = (double)hdr[LR_ADE_HDR_DEATHS];
-    const int n_cls = (int)hdr[LR_ADE_HDR_CLASSES];
+    const double D = (double)d.hdr[LR_ADE_HDR_DEATHS];
+    const int n_cls = lr_ade_class_count(d, A);
     if (D == 0.0) {
         if (tid == 0) out_ll[o] = 0.0, out_c[o] = 0.0;
         return;
     }
     double e_part = 0.0, zero = 0.0;
     for (int j = tid; j < A; j += LR_ADE_THREADS) {
+        // (not lr_adej_weight: exp(k log j) from logs kept across iterations rounds differently from pow(j, k))
         const double w = j == 0 ? 1.0 : pow((double)j, k) * expm1(k * log1p(1.0 / (double)j));
         s_w[j] = w;
         s_mu[j] = mu_bins[(size_t)s * A + j];
@@ -311,29 +325,23 @@ __global__ __launch_bounds__(LR_ADE_THREADS) void lr_ade_profile_kernel(
 // ------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------
-struct lr_ade_ws {
-    size_t hdr, death_bin, cls_cell, cls_n, R, M, total;
-};
-
 static int lr_ade_sizes(int n_bins, int S, int G) {
     if (S < 1 || G < 1 || n_bins < 1 || n_bins > LR_ADE_MAX_BINS) return LR_ERR_SIZE;
     if ((long long)S * G >= (1ll << 31)) return LR_ERR_SIZE;
     return LR_OK;
 }
 
-// workspace: [hdr | death_bin | cls_cell | cls_n | R | M], each 256-byte aligned
-static lr_ade_ws lr_ade_layout(int A, int S) {
-    lr_ade_ws w;
-    const long long most = (long long)A * (A + 1) / 2;
-    size_t o = 0;
-    w.hdr = o, o += 256;
-    w.death_bin = o, o += lr_align_up64((long long)A * sizeof(int), 256);
-    w.cls_cell = o, o += lr_align_up64(most * sizeof(int), 256);
-    w.cls_n = o, o += lr_align_up64(most * sizeof(double), 256);
-    w.R = o, o += lr_align_up64((long long)A * A * sizeof(double), 256);
-    w.M = o, o += lr_align_up64((long long)S * A * sizeof(double), 256);
-    w.total = o;
-    return w;
+int lr_ade_prepare_tables(const int64_t* dead, const int64_t* cens, int A, void* tables, hipStream_t stream) {
+    const lr_ade_ws w = lr_ade_layout(A);
+    char* base = (char*)tables;
+    hipLaunchKernelGGL(lr_ade_prep_kernel, dim3(1), dim3(LR_ADE_PREP_THREADS), 0, stream, (const long long*)dead,
+                       (const long long*)cens, A, (int*)(base + w.cls_cell), (double*)(base + w.cls_n), (int*)(base + w.cls_n32),
+                       (int*)(base + w.death_bin), (long long*)(base + w.hdr));
+    const int rc = (int)hipGetLastError();
+    if (rc) return rc;
+    hipLaunchKernelGGL(lr_ade_risk_kernel, dim3((A + LR_ADE_THREADS - 1) / LR_ADE_THREADS), dim3(LR_ADE_THREADS), 0, stream,
+                       (const long long*)dead, (const long long*)cens, A, (double*)(base + w.R), (int*)(base + w.R32));
+    return (int)hipGetLastError();
 }
 
 extern "C" int lr_ade_classes(const double* ts, const double* te, int64_t n, double t0, int32_t n_bins, int64_t* out_dead,
@@ -356,10 +364,15 @@ extern "C" int lr_ade_classes(const double* ts, const double* te, int64_t n, dou
     return (int)hipGetLastError();
 }
 
+// workspace: [the tables (lr_ade_tables.h) | M [S, A]]
+static int64_t lr_ade_profile_bytes(int A, int S) {
+    return (int64_t)lr_ade_layout(A).total + lr_align_up64((long long)S * A * sizeof(double), 256);
+}
+
 extern "C" int64_t lr_ade_profile_workspace_bytes(int32_t n_bins, int32_t S, int32_t G) {
     const int rc = lr_ade_sizes(n_bins, S, G);
     if (rc != LR_OK) return rc;
-    return (int64_t)lr_ade_layout(n_bins, S).total;
+    return lr_ade_profile_bytes(n_bins, S);
 }
 
 extern "C" int lr_ade_profile(const int64_t* dead, const int64_t* cens, int32_t n_bins, const double* mu_bins, int32_t S,
@@ -369,30 +382,17 @@ extern "C" int lr_ade_profile(const int64_t* dead, const int64_t* cens, int32_t 
     int rc = lr_ade_sizes(n_bins, S, G);
     if (rc != LR_OK) return rc;
     const int A = n_bins;
-    const lr_ade_ws w = lr_ade_layout(A, S);
-    if ((int64_t)w.total > workspace_bytes) return LR_ERR_WORKSPACE;
+    if (lr_ade_profile_bytes(A, S) > workspace_bytes) return LR_ERR_WORKSPACE;
     hipStream_t stream = (hipStream_t)stream_;
-    char* base = (char*)workspace;
-    long long* hdr = (long long*)(base + w.hdr);
-    int* death_bin = (int*)(base + w.death_bin);
-    int* cls_cell = (int*)(base + w.cls_cell);
-    double* cls_n = (double*)(base + w.cls_n);
-    double* R = (double*)(base + w.R);
-    double* M = (double*)(base + w.M);
-    hipLaunchKernelGGL(lr_ade_prep_kernel, dim3(1), dim3(LR_ADE_PREP_THREADS), 0, stream, (const long long*)dead, A, cls_cell,
-                       cls_n, death_bin, hdr);
-    rc = (int)hipGetLastError();
+    const lr_ade_data d = lr_ade_view(workspace, A);
+    double* M = (double*)((char*)workspace + lr_ade_layout(A).total);
+    rc = lr_ade_prepare_tables(dead, cens, A, workspace, stream);
     if (rc) return rc;
-    hipLaunchKernelGGL(lr_ade_risk_kernel, dim3((A + LR_ADE_THREADS - 1) / LR_ADE_THREADS), dim3(LR_ADE_THREADS), 0, stream,
-                       (const long long*)dead, (const long long*)cens, A, R);
-    rc = (int)hipGetLastError();
-    if (rc) return rc;
-    hipLaunchKernelGGL(lr_ade_draw_kernel, dim3(S), dim3(LR_ADE_THREADS), 0, stream, mu_bins, A, (const double*)R,
-                       (const int*)death_bin, M, (int*)out_flag);
+    hipLaunchKernelGGL(lr_ade_draw_kernel, dim3(S), dim3(LR_ADE_THREADS), 0, stream, mu_bins, A, d.R, d.death_bin, M,
+                       (int*)out_flag);
     rc = (int)hipGetLastError();
     if (rc) return rc;
     hipLaunchKernelGGL(lr_ade_profile_kernel, dim3((unsigned)((long long)S * G)), dim3(LR_ADE_THREADS), 0, stream, mu_bins, A,
-                       shapes, G, (const int*)cls_cell, (const double*)cls_n, (const long long*)hdr, (const double*)M,
-                       (const int*)out_flag, out_ll, out_c);
+                       shapes, G, d, (const double*)M, (const int*)out_flag, out_ll, out_c);
     return (int)hipGetLastError();
 }

@@ -1,9 +1,7 @@
 // lr_adej.hip - age-dependent extinction sampled jointly (include/literate_hip_adej.h): a Metropolis-Hastings sampler over
 // (the death-rate skyline, the Weibull shape), one workgroup of four waves per chain, every chain's launch inside one kernel.
 //
-//   lr_adej_prep_kernel    one block: the classes with a count in the table's own order (a ballot scan: one order for every
-//                          later sum), the bins that hold a death, the header
-//   lr_adej_risk_kernel    R[jb][j] = cens[jb] + sum_{a > j} dead[jb][a], as a packed triangle (row jb holds A - jb numbers)
+//   (lr_ade_prepare_tables of lr_ade.hip writes the workspace: the tables of lr_ade_tables.h)
 //   lr_adej_loglik_kernel  one block per row: l(mu, k)
 //   lr_adej_chain_kernel   one block per chain: its initial state, or n_iters iterations from its state
 //
@@ -25,8 +23,8 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/literate_hip_adej.h"
+#include "lr_ade_tables.h"
 #include "lr_chain.h"
-#include "lr_internal.h"
 
 // draw purposes of this sampler, beside the engines' LR_P_MOVE, LR_P_MULT, LR_P_RJ, LR_P_BETA_A / _B and LR_P_ACCEPT
 #define LR_P_ADEJ_SHAPE 48
@@ -36,11 +34,7 @@
 
 #define LR_ADEJ_THREADS 256
 #define LR_ADEJ_WAVES (LR_ADEJ_THREADS / 64)
-#define LR_ADEJ_PREP_THREADS 1024
 #define LR_ADEJ_LDS_CLASSES 1024
-#define LR_ADEJ_HDR_CLASSES 0
-#define LR_ADEJ_HDR_DEATHS 1
-#define LR_ADEJ_HDR_FITS32 2      /* every class count and every number at risk is below 2^31 */
 #define LR_ADEJ_LOG_SHAPE_MAX 2.0794415416798357   /* log 8 */
 #define LR_ADEJ_INIT_RATE_SCALE 0.2
 #define LR_ADEJ_INIT_LOG_SHAPE_SPAN 2.772588722239781 /* 2 log 4 */
@@ -61,6 +55,7 @@
 static_assert(LR_ADEJ_S_TIMES + LR_KMAX + 1 <= LR_ADEJ_STATE_W, "the state holds K + 1 times");
 static_assert(LR_ADEJ_ROW_W == LR_ADEJ_ROW_HEAD + 2 * LR_KMAX - 1, "row layout");
 static_assert(LR_ADEJ_MAX_BINS <= LR_ADEJ_THREADS / 2, "a thread per bin, two partial sums per age");
+static_assert(LR_ADEJ_MAX_BINS <= LR_ADE_MAX_BINS, "the tables are prepared for up to LR_ADE_MAX_BINS bins");
 
 struct lr_adej_cfg {
     double t0, win, poisson_prior, mult_l, log_A;
@@ -69,109 +64,9 @@ struct lr_adej_cfg {
     int chain0, n_chains;
 };
 
-// what a kernel reads of the workspace
-struct lr_adej_data {
-    const long long* hdr;
-    const int* death_bin;
-    const int* cls_cell;      // je | a << 16
-    const double* cls_n;
-    const int* cls_n32;
-    const double* R;          // packed triangle
-    const int* R32;
-};
-
 // ------------------------------------------------------------------------------------------
 // device side
 // ------------------------------------------------------------------------------------------
-__host__ __device__ __forceinline__ int lr_adej_row(int jb, int A) { return jb * A - (jb * (jb - 1)) / 2; }
-
-// one block.  cls_cell[p] = je | a << 16, cls_n[p] / cls_n32[p] = the count; death_bin[je] = 1 where a death was observed
-__global__ __launch_bounds__(LR_ADEJ_PREP_THREADS) void lr_adej_prep_kernel(const long long* __restrict__ dead,
-                                                                            const long long* __restrict__ cens, int A,
-                                                                            int* __restrict__ cls_cell,
-                                                                            double* __restrict__ cls_n,
-                                                                            int* __restrict__ cls_n32,
-                                                                            int* __restrict__ death_bin,
-                                                                            long long* __restrict__ hdr) {
-    __shared__ int s_wave[LR_ADEJ_PREP_THREADS / 64];
-    __shared__ int s_bin[LR_ADEJ_MAX_BINS];
-    __shared__ unsigned long long s_deaths;
-    __shared__ unsigned long long s_most;                  // the largest number of lineages of one birth bin
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    for (int i = tid; i < A; i += LR_ADEJ_PREP_THREADS) s_bin[i] = 0;
-    if (tid == 0) s_deaths = 0ull, s_most = 0ull;
-    __syncthreads();
-    const int cells = A * A;
-    int base_pos = 0;
-    unsigned long long mine = 0ull;
-    for (int base = 0; base < cells; base += LR_ADEJ_PREP_THREADS) {
-        const int e = base + tid;
-        long long v = 0;
-        int jb = 0, a = 0;
-        if (e < cells) {
-            jb = e / A, a = e - jb * A;
-            if (jb + a < A) v = dead[e];
-        }
-        const bool is = v > 0;
-        const unsigned long long votes = __ballot(is);
-        if (lane == 0) s_wave[wave] = __popcll(votes);
-        __syncthreads();
-        int before = 0, all = 0;
-        for (int w = 0; w < LR_ADEJ_PREP_THREADS / 64; ++w) {
-            const int c = s_wave[w];
-            before += w < wave ? c : 0;
-            all += c;
-        }
-        if (is) {
-            const int p = base_pos + before + __popcll(votes & ((1ull << lane) - 1ull));
-            cls_cell[p] = (jb + a) | (a << 16);
-            cls_n[p] = (double)v;
-            cls_n32[p] = (int)(v < INT_MAX ? v : INT_MAX);
-            s_bin[jb + a] = 1;
-            mine += (unsigned long long)v;
-        }
-        base_pos += all;
-        __syncthreads();
-    }
-    if (mine) atomicAdd(&s_deaths, mine);
-    // a birth bin's lineages: R[jb][0] plus its deaths at age 0, the largest number any R or class count can reach
-    for (int jb = tid; jb < A; jb += LR_ADEJ_PREP_THREADS) {
-        unsigned long long tot = (unsigned long long)(cens[jb] > 0 ? cens[jb] : 0);
-        for (int a = 0; a < A - jb; ++a) {
-            const long long v = dead[(size_t)jb * A + a];
-            tot += (unsigned long long)(v > 0 ? v : 0);
-        }
-        atomicMax(&s_most, tot);
-    }
-    __syncthreads();
-    for (int i = tid; i < A; i += LR_ADEJ_PREP_THREADS) death_bin[i] = s_bin[i];
-    if (tid == 0) {
-        hdr[LR_ADEJ_HDR_CLASSES] = base_pos, hdr[LR_ADEJ_HDR_DEATHS] = (long long)s_deaths;
-        hdr[LR_ADEJ_HDR_FITS32] = s_most < (unsigned long long)INT_MAX ? 1 : 0;
-    }
-}
-
-__global__ __launch_bounds__(LR_ADEJ_THREADS) void lr_adej_risk_kernel(const long long* __restrict__ dead,
-                                                                      const long long* __restrict__ cens, int A,
-                                                                      double* __restrict__ R, int* __restrict__ R32) {
-    const int jb = blockIdx.x * LR_ADEJ_THREADS + threadIdx.x;
-    if (jb >= A) return;
-    long long run = cens[jb] > 0 ? cens[jb] : 0;
-    const int row = lr_adej_row(jb, A);
-    for (int j = A - jb - 1; j >= 0; --j) {
-        R[row + j] = (double)run;
-        R32[row + j] = (int)(run < INT_MAX ? run : INT_MAX);
-        const long long v = dead[(size_t)jb * A + j];
-        run += v > 0 ? v : 0;
-    }
-}
-
-// the number of classes, kept inside the list's room whatever the workspace holds
-__device__ __forceinline__ int lr_adej_classes(const lr_adej_data& d, int A) {
-    const long long n = d.hdr[LR_ADEJ_HDR_CLASSES];
-    return (int)(n < 0 ? 0 : (n > (long long)A * (A + 1) / 2 ? (long long)A * (A + 1) / 2 : n));
-}
-
 // the LDS of a likelihood evaluation; the chain kernel carves R32 [A (A + 1) / 2] behind it (dynamic LDS only: its base
 // stays 16-byte aligned)
 struct lr_adej_lds {
@@ -189,6 +84,7 @@ struct lr_adej_lds {
 static_assert(sizeof(lr_adej_lds) % 16 == 0, "R32 behind the struct starts 16-byte aligned");
 
 // x summed over the block, the same in every thread
+// (not lr_ade_sum2: that one adds the lanes in a __shfl_down tree, and the bits would differ)
 __device__ __forceinline__ double lr_adej_block_sum(double x, double* s_red) {
     const double v = lr_wave_sum(x);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -201,12 +97,8 @@ __device__ __forceinline__ double lr_adej_block_sum(double x, double* s_red) {
     return t;
 }
 
-// n log(1 - exp(-x)): accurate from the smallest x to the largest
-__device__ __forceinline__ double lr_adej_term(double n, double x) {
-    return n * (x < 0.6931471805599453 ? log(-expm1(-x)) : log1p(-exp(-x)));
-}
-
 // w_k[j] of this thread's age j = tid (lj = log j, l1 = log1p(1 / j))
+// (not lr_ade_profile_kernel's pow(j, k): the logs are kept across iterations, and exp(k log j) rounds differently)
 __device__ __forceinline__ double lr_adej_weight(int j, double k, double lj, double l1) {
     return j == 0 ? 1.0 : exp(k * lj) * expm1(k * l1);
 }
@@ -222,9 +114,9 @@ __device__ __forceinline__ void lr_adej_risk_sums(int A, const double* mu, doubl
     double acc = 0.0;
     if (j < A) {
         if (r32) {
-            for (int jb = p; jb < A - j; jb += P) acc = fma((double)r32[lr_adej_row(jb, A) + j], mu[jb + j], acc);
+            for (int jb = p; jb < A - j; jb += P) acc = fma((double)r32[lr_ade_row(jb, A) + j], mu[jb + j], acc);
         } else {
-            for (int jb = p; jb < A - j; jb += P) acc = fma(rg[lr_adej_row(jb, A) + j], mu[jb + j], acc);
+            for (int jb = p; jb < A - j; jb += P) acc = fma(rg[lr_ade_row(jb, A) + j], mu[jb + j], acc);
         }
     }
     part[tid] = acc;
@@ -239,24 +131,24 @@ __device__ __forceinline__ void lr_adej_risk_sums(int A, const double* mu, doubl
 
 // l(mu, k) from w, M and mu in LDS; the classes from LDS (s_cell) or the workspace.  The same value in every thread.
 __device__ __forceinline__ double lr_adej_eval(int A, int n_cls, const double* w, const double* M, const double* mu,
-                                               const int* s_cell, const int* s_n, const lr_adej_data& d, double* s_red) {
+                                               const int* s_cell, const int* s_n, const lr_ade_data& d, double* s_red) {
     const int tid = threadIdx.x;
     double acc = tid < A ? -(w[tid] * M[tid]) : 0.0;
     if (s_cell) {
         for (int i = tid; i < n_cls; i += LR_ADEJ_THREADS) {
             const int cell = s_cell[i];
-            acc += lr_adej_term((double)s_n[i], mu[cell & 0xFFFF] * w[cell >> 16]);
+            acc += lr_ade_term((double)s_n[i], mu[cell & 0xFFFF] * w[cell >> 16]);
         }
     } else {
         for (int i = tid; i < n_cls; i += LR_ADEJ_THREADS) {
             const int cell = d.cls_cell[i];
-            acc += lr_adej_term(d.cls_n[i], mu[cell & 0xFFFF] * w[cell >> 16]);
+            acc += lr_ade_term(d.cls_n[i], mu[cell & 0xFFFF] * w[cell >> 16]);
         }
     }
     return lr_adej_block_sum(acc, s_red);
 }
 
-__global__ __launch_bounds__(LR_ADEJ_THREADS) void lr_adej_loglik_kernel(lr_adej_data d, int A,
+__global__ __launch_bounds__(LR_ADEJ_THREADS) void lr_adej_loglik_kernel(lr_ade_data d, int A,
                                                                         const double* __restrict__ mu_bins,
                                                                         const double* __restrict__ shapes,
                                                                         double* __restrict__ out_ll,
@@ -269,7 +161,7 @@ __global__ __launch_bounds__(LR_ADEJ_THREADS) void lr_adej_loglik_kernel(lr_adej
     if (tid < A) {
         const double m = mu_bins[(size_t)row * A + tid];
         s.mu[tid] = m;
-        bad = !(m >= 0.0) || !(m < __builtin_inf()) || (m == 0.0 && d.death_bin[tid]);
+        bad = lr_ade_bad_rate(m, d.death_bin, tid);
     }
     bad = __syncthreads_or(bad) ? 1 : 0;
     if (!(k > 0.0) || !(k < __builtin_inf())) bad |= 2;
@@ -280,7 +172,7 @@ __global__ __launch_bounds__(LR_ADEJ_THREADS) void lr_adej_loglik_kernel(lr_adej
     }
     if (tid < A) s.w[tid] = lr_adej_weight(tid, k, tid ? log((double)tid) : 0.0, tid ? log1p(1.0 / (double)tid) : 0.0);
     lr_adej_risk_sums(A, s.mu, s.M, s.part, nullptr, d.R);
-    const double ll = lr_adej_eval(A, lr_adej_classes(d, A), s.w, s.M, s.mu, nullptr, nullptr, d, s.red);
+    const double ll = lr_adej_eval(A, lr_ade_class_count(d, A), s.w, s.M, s.mu, nullptr, nullptr, d, s.red);
     if (tid == 0) out_ll[row] = ll, out_flag[row] = 0;
 }
 
@@ -295,7 +187,7 @@ __device__ __forceinline__ void lr_adej_expand(int A, int K, const lr_adej_lds& 
 }
 
 // mode 0: lr_adej_init; mode 1: n_iters iterations from it0
-__global__ __launch_bounds__(LR_ADEJ_THREADS) void lr_adej_chain_kernel(lr_adej_data d, lr_adej_cfg cfg, int mode,
+__global__ __launch_bounds__(LR_ADEJ_THREADS) void lr_adej_chain_kernel(lr_ade_data d, lr_adej_cfg cfg, int mode,
                                                                        double* __restrict__ state, long long it0,
                                                                        long long n_iters, double* __restrict__ rows) {
     extern __shared__ __attribute__((aligned(16))) char lr_adej_smem[];
@@ -303,8 +195,8 @@ __global__ __launch_bounds__(LR_ADEJ_THREADS) void lr_adej_chain_kernel(lr_adej_
     int* s_R32 = reinterpret_cast<int*>(lr_adej_smem + sizeof(lr_adej_lds));
     const int c = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int A = cfg.A;
-    const int n_cls = lr_adej_classes(d, A);
-    const bool fits = d.hdr[LR_ADEJ_HDR_FITS32] != 0;
+    const int n_cls = lr_ade_class_count(d, A);
+    const bool fits = d.hdr[LR_ADE_HDR_FITS32] != 0;
     const int* r32 = fits ? s_R32 : nullptr;
     const int* s_cell = fits && n_cls <= LR_ADEJ_LDS_CLASSES ? s.cls_cell : nullptr;
     const int* s_n = s.cls_n;
@@ -526,44 +418,11 @@ __global__ __launch_bounds__(LR_ADEJ_THREADS) void lr_adej_chain_kernel(lr_adej_
 // ------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------
-struct lr_adej_ws {
-    size_t hdr, death_bin, cls_cell, cls_n, cls_n32, R, R32, total;
-};
-
-// workspace: [hdr | death_bin | cls_cell | cls_n | cls_n32 | R | R32], each 256-byte aligned
-static lr_adej_ws lr_adej_layout(int A) {
-    lr_adej_ws w;
-    const long long tri = (long long)A * (A + 1) / 2;
-    size_t o = 0;
-    w.hdr = o, o += 256;
-    w.death_bin = o, o += lr_align_up64((long long)A * sizeof(int), 256);
-    w.cls_cell = o, o += lr_align_up64(tri * sizeof(int), 256);
-    w.cls_n = o, o += lr_align_up64(tri * sizeof(double), 256);
-    w.cls_n32 = o, o += lr_align_up64(tri * sizeof(int), 256);
-    w.R = o, o += lr_align_up64(tri * sizeof(double), 256);
-    w.R32 = o, o += lr_align_up64(tri * sizeof(int), 256);
-    w.total = o;
-    return w;
-}
-
-static lr_adej_data lr_adej_view(const void* workspace, const lr_adej_ws& w) {
-    const char* base = (const char*)workspace;
-    lr_adej_data d;
-    d.hdr = (const long long*)(base + w.hdr);
-    d.death_bin = (const int*)(base + w.death_bin);
-    d.cls_cell = (const int*)(base + w.cls_cell);
-    d.cls_n = (const double*)(base + w.cls_n);
-    d.cls_n32 = (const int*)(base + w.cls_n32);
-    d.R = (const double*)(base + w.R);
-    d.R32 = (const int*)(base + w.R32);
-    return d;
-}
-
 static bool lr_adej_bins_ok(int n_bins) { return n_bins >= 1 && n_bins <= LR_ADEJ_MAX_BINS; }
 
 extern "C" int64_t lr_adej_workspace_bytes(int32_t n_bins) {
     if (!lr_adej_bins_ok(n_bins)) return LR_ERR_SIZE;
-    return (int64_t)lr_adej_layout(n_bins).total;
+    return (int64_t)lr_ade_layout(n_bins).total;
 }
 
 extern "C" int lr_adej_prepare(const int64_t* dead, const int64_t* cens, int32_t n_bins, void* workspace,
@@ -571,28 +430,17 @@ extern "C" int lr_adej_prepare(const int64_t* dead, const int64_t* cens, int32_t
     if (!dead || !cens || !workspace) return LR_ERR_NULL;
     if (!lr_adej_bins_ok(n_bins)) return LR_ERR_SIZE;
     const int A = n_bins;
-    const lr_adej_ws w = lr_adej_layout(A);
-    if ((int64_t)w.total > workspace_bytes) return LR_ERR_WORKSPACE;
-    hipStream_t stream = (hipStream_t)stream_;
-    char* base = (char*)workspace;
-    hipLaunchKernelGGL(lr_adej_prep_kernel, dim3(1), dim3(LR_ADEJ_PREP_THREADS), 0, stream, (const long long*)dead,
-                       (const long long*)cens, A, (int*)(base + w.cls_cell), (double*)(base + w.cls_n), (int*)(base + w.cls_n32),
-                       (int*)(base + w.death_bin), (long long*)(base + w.hdr));
-    int rc = (int)hipGetLastError();
-    if (rc) return rc;
-    hipLaunchKernelGGL(lr_adej_risk_kernel, dim3((A + LR_ADEJ_THREADS - 1) / LR_ADEJ_THREADS), dim3(LR_ADEJ_THREADS), 0, stream,
-                       (const long long*)dead, (const long long*)cens, A, (double*)(base + w.R), (int*)(base + w.R32));
-    return (int)hipGetLastError();
+    if ((int64_t)lr_ade_layout(A).total > workspace_bytes) return LR_ERR_WORKSPACE;
+    return lr_ade_prepare_tables(dead, cens, A, workspace, (hipStream_t)stream_);
 }
 
 extern "C" int lr_adej_loglik(const void* workspace, int64_t workspace_bytes, int32_t n_bins, const double* mu_bins,
                               const double* shapes, int32_t S, double* out_ll, int32_t* out_flag, void* stream_) {
     if (!workspace || !mu_bins || !shapes || !out_ll || !out_flag) return LR_ERR_NULL;
     if (S < 1 || !lr_adej_bins_ok(n_bins)) return LR_ERR_SIZE;
-    const lr_adej_ws w = lr_adej_layout(n_bins);
-    if ((int64_t)w.total > workspace_bytes) return LR_ERR_WORKSPACE;
+    if ((int64_t)lr_ade_layout(n_bins).total > workspace_bytes) return LR_ERR_WORKSPACE;
     hipLaunchKernelGGL(lr_adej_loglik_kernel, dim3((unsigned)S), dim3(LR_ADEJ_THREADS), sizeof(lr_adej_lds), (hipStream_t)stream_,
-                       lr_adej_view(workspace, w), (int)n_bins, mu_bins, shapes, out_ll, (int*)out_flag);
+                       lr_ade_view(workspace, n_bins), (int)n_bins, mu_bins, shapes, out_ll, (int*)out_flag);
     return (int)hipGetLastError();
 }
 
@@ -601,14 +449,14 @@ static int lr_adej_chain_args(const void* workspace, int64_t workspace_bytes, in
                               int32_t n_chains, const double* state, int64_t it0, int64_t n_iters, int32_t s_freq,
                               const double* rows, int64_t n_rows, bool steps, lr_adej_cfg* cfg) {
     // (rows may be NULL where no row is due)
-    const bool counts_ok = steps && it0 >= 0 && n_iters >= 0 && s_freq >= 1 && it0 <= INT64_MAX - n_iters - s_freq;
-    const int64_t need = counts_ok ? (it0 + n_iters + s_freq - 1) / s_freq - (it0 + s_freq - 1) / s_freq : 0;
+    int64_t need;
+    const bool counts_ok = lr_rows_due(it0, n_iters, s_freq, &need);
     if (!workspace || !state || (steps && !rows && !(counts_ok && need == 0))) return LR_ERR_NULL;
     if (!lr_adej_bins_ok(n_bins) || n_chains < 1 || chain0 < 0) return LR_ERR_SIZE;
     if (steps && (!counts_ok || n_rows < need)) return LR_ERR_SIZE;
     if (!std::isfinite(win) || !std::isfinite(poisson_prior) || !(win > 0.0) || poisson_prior < 0.0) return LR_ERR_MODEL;
     if (!std::isfinite(t0) || t0 != std::floor(t0)) return LR_ERR_T0;
-    if ((int64_t)lr_adej_layout(n_bins).total > workspace_bytes) return LR_ERR_WORKSPACE;
+    if ((int64_t)lr_ade_layout(n_bins).total > workspace_bytes) return LR_ERR_WORKSPACE;
     cfg->t0 = t0, cfg->win = win, cfg->poisson_prior = poisson_prior;
     cfg->mult_l = 2.0 * std::log(LR_MULT_D), cfg->log_A = std::log((double)n_bins);
     cfg->A = n_bins, cfg->const_rates = const_rates ? 1 : 0, cfg->use_rate_hp = use_rate_hp ? 1 : 0, cfg->s_freq = steps ? s_freq : 1;
@@ -626,7 +474,7 @@ extern "C" int lr_adej_init(const void* workspace, int64_t workspace_bytes, int3
                                       chain0, n_chains, state, 0, 0, 1, nullptr, 0, false, &cfg);
     if (rc != LR_OK) return rc;
     hipLaunchKernelGGL(lr_adej_chain_kernel, dim3((unsigned)n_chains), dim3(LR_ADEJ_THREADS), lr_adej_chain_lds(n_bins),
-                       (hipStream_t)stream_, lr_adej_view(workspace, lr_adej_layout(n_bins)), cfg, 0, state, 0ll, 0ll,
+                       (hipStream_t)stream_, lr_ade_view(workspace, n_bins), cfg, 0, state, 0ll, 0ll,
                        (double*)nullptr);
     return (int)hipGetLastError();
 }
@@ -641,7 +489,7 @@ extern "C" int lr_adej_steps(const void* workspace, int64_t workspace_bytes, int
     if (rc != LR_OK) return rc;
     if (n_iters == 0) return LR_OK;
     hipLaunchKernelGGL(lr_adej_chain_kernel, dim3((unsigned)n_chains), dim3(LR_ADEJ_THREADS), lr_adej_chain_lds(n_bins),
-                       (hipStream_t)stream_, lr_adej_view(workspace, lr_adej_layout(n_bins)), cfg, 1, state, (long long)it0,
+                       (hipStream_t)stream_, lr_ade_view(workspace, n_bins), cfg, 1, state, (long long)it0,
                        (long long)n_iters, rows);
     return (int)hipGetLastError();
 }

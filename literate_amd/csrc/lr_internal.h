@@ -59,5 +59,13 @@ static inline int lr_env_int(const char* name, int dflt) {
     return v ? atoi(v) : dflt;
 }
 
+// the rows due from a `steps` call (lr_adej_steps, lr_mlik_steps): iterations it0 .. it0 + n_iters - 1, a row after every one
+// with it % s_freq == 0.  false: a count is out of range, or their sum would overflow (*need = 0 then)
+static inline bool lr_rows_due(int64_t it0, int64_t n_iters, int32_t s_freq, int64_t* need) {
+    const bool ok = it0 >= 0 && n_iters >= 0 && s_freq >= 1 && it0 <= INT64_MAX - n_iters - s_freq;
+    *need = ok ? (it0 + n_iters + s_freq - 1) / s_freq - (it0 + s_freq - 1) / s_freq : 0;
+    return ok;
+}
+
 static inline int lr_align_up(long long x, long long a) { return (int)((x + a - 1) / a * a); }
 static inline long long lr_align_up64(long long x, long long a) { return (x + a - 1) / a * a; }

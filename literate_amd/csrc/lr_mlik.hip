@@ -20,6 +20,7 @@
 
 #include "../../include/literate_hip_mlik.h"
 #include "lr_dd.h"
+#include "lr_internal.h"
 
 #define LR_MLIK_THREADS 256
 #define LR_MLIK_WAVES (LR_MLIK_THREADS / LR_WAVE)
@@ -277,8 +278,8 @@ static int lr_mlik_chain_args(const double* n_spec, const double* n_exti, const 
                               const double* state, int64_t it0, int64_t n_iters, int32_t s_freq, const double* rows,
                               int64_t n_rows, bool steps, lr_mlik_cfg* cfg, lr_mlik_temps* tp) {
     // (rows may be NULL where no row is due)
-    const bool counts_ok = steps && it0 >= 0 && n_iters >= 0 && s_freq >= 1 && it0 <= INT64_MAX - n_iters - s_freq;
-    const int64_t need = counts_ok ? (it0 + n_iters + s_freq - 1) / s_freq - (it0 + s_freq - 1) / s_freq : 0;
+    int64_t need;
+    const bool counts_ok = lr_rows_due(it0, n_iters, s_freq, &need);
     if (!n_spec || !n_exti || !DT || !betas || !scales || !state || (steps && !rows && !(counts_ok && need == 0)))
         return LR_ERR_NULL;
     if (n_bins < 1 || n_bins > LR_MLIK_MAX_BINS || T < 2 || T > LR_MLIK_MAX_TEMPS || n_reps < 1 || rep0 < 0) return LR_ERR_SIZE;

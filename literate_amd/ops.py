@@ -893,7 +893,8 @@ def adej_init(data, t0, n_chains, seed, settings=AdejSettings(), chain0=0, out=N
     return state
 
 
-def adej_rows_needed(it0, n_iters, s_freq):
+def rows_due(it0, n_iters, s_freq):
+    """the rows of a `steps` call (adej_steps, mlik_steps): one per iteration it0 .. it0 + n_iters - 1 with it % s_freq == 0"""
     s = int(s_freq)
     return (int(it0) + int(n_iters) + s - 1) // s - (int(it0) + s - 1) // s
 
@@ -908,7 +909,7 @@ def adej_steps(data, t0, state, it0, n_iters, s_freq, seed, settings=AdejSetting
             or state.device != data.device:
         raise ValueError("state must be adej_init's [chains, LR_ADEJ_STATE_W] float64 tensor on the data's device")
     C = int(state.shape[0])
-    n = adej_rows_needed(it0, n_iters, s_freq) if int(s_freq) >= 1 and int(n_iters) >= 0 and int(it0) >= 0 else 0
+    n = rows_due(it0, n_iters, s_freq) if int(s_freq) >= 1 and int(n_iters) >= 0 and int(it0) >= 0 else 0
     (rows,) = _ade_out(out, ((max(n, 0), C, _hip.LR_ADEJ_ROW_W),), (torch.float64,), data.device, "(rows,)")
     rc = _hip.launch(lib.lr_adej_steps, data.device, *_adej_args(data, t0, settings, seed, chain0, C), _hip.ptr(state), int(it0),
                      int(n_iters), int(s_freq), _hip.ptr(rows) if rows.numel() else None, n)
@@ -984,7 +985,7 @@ def mlik_steps(data, betas, scales, state, it0, n_iters, s_freq, seed, rep0=0, o
             or not state.is_contiguous() or state.device != data.device:
         raise ValueError("state must be mlik_init's [replicates, T, LR_MLIK_STATE_W] float64 tensor on the data's device")
     R = int(state.shape[0])
-    n = adej_rows_needed(it0, n_iters, s_freq) if int(s_freq) >= 1 and int(n_iters) >= 0 and int(it0) >= 0 else 0
+    n = rows_due(it0, n_iters, s_freq) if int(s_freq) >= 1 and int(n_iters) >= 0 and int(it0) >= 0 else 0
     (rows,) = _ade_out(out, ((max(n, 0), R, int(b.size), _hip.LR_MLIK_ROW_W),), (torch.float64,), data.device, "(rows,)")
     rc = _hip.launch(lib.lr_mlik_steps, data.device, *_mlik_args(data, b, s, seed, rep0, R), _hip.ptr(state), int(it0), int(n_iters),
                      int(s_freq), _hip.ptr(rows) if rows.numel() else None, n)

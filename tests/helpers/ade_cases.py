@@ -183,6 +183,26 @@ def case_profile(group):
             assert (dl <= 1.0).all() and (dc <= C_TOL).all()
 
 
+BIG_SHIFT, BIG_SHAPES = 28, (0.125, 1.0, 8.0)
+
+
+def case_big_counts():
+    """counts beyond 32 bits: a40's table times 2^28 against the table itself.  A power of two scales every product and sum
+    of the likelihood exactly and the iteration works on log c, which does not move: the same c^ bit for bit, l^ times 2^28
+    exactly.  A profile that read a count clamped to 32 bits would fail both."""
+    dead, cens, mu, _ = profile_inputs("a40")
+    mu, shapes = mu[:2], np.array(BIG_SHAPES)
+    big_dead, big_cens = dead << BIG_SHIFT, cens << BIG_SHIFT
+    most = int((big_cens + big_dead.sum(axis=1)).max())
+    say("largest number of lineages of one birth bin: %d, largest class: %d" % (most, int(big_dead.max())))
+    assert most > 2 ** 31 - 1
+    base, big = host(dev_profile(dead, cens, mu, shapes)), host(dev_profile(big_dead, big_cens, mu, shapes))
+    assert np.isfinite(base[0]).all() and (base[1] > 0).all()
+    same("flags", [base[2].tolist(), big[2].tolist()], [[0, 0], [0, 0]])
+    same("c of the scaled table", big[1].tobytes(), base[1].tobytes())
+    same("l of the scaled table against 2^%d l" % BIG_SHIFT, big[0], float(1 << BIG_SHIFT) * base[0])
+
+
 def case_degenerate():
     """no observed death: c = 0, l = 0; three deaths in the one class of one bin and nothing censored: c = +inf, l = 0"""
     rng = np.random.default_rng(311)

@@ -126,7 +126,11 @@ RTOL = ATOL = 1e-9
 def traj_table(name):
     if name == "big12":
         dead, cens = table("a12")
-        return dead * (1 << 24), cens * (1 << 24)
+        dead, cens = dead * (1 << 28), cens * (1 << 28)
+        # (the name's condition: a birth bin with more lineages than 32 bits hold, so FITS32 is 0 and the chain kernel reads
+        # the doubles of R and of the class list from the workspace)
+        assert int((cens + dead.sum(axis=1)).max()) > 2 ** 31 - 1
+        return dead, cens
     return table(name)
 
 
@@ -368,7 +372,7 @@ def case_function():
         rows, state = ops.adej_run(data, 0.0, C, n_it, s, seed, st)
         state2 = torch.full_like(state, 123.0)
         ops.adej_init(data, 0.0, C, seed, st, out=(state2,))
-        dirty = torch.full((ops.adej_rows_needed(0, n_a, s), C, rows.shape[2]), 123.0, dtype=torch.float64, device="cuda")
+        dirty = torch.full((ops.rows_due(0, n_a, s), C, rows.shape[2]), 123.0, dtype=torch.float64, device="cuda")
         ra = ops.adej_steps(data, 0.0, state2, 0, n_a, s, seed, st, out=(dirty,))
         rb = ops.adej_steps(data, 0.0, state2, n_a, n_it - n_a, s, seed, st)
         same("%s: %d + %d iterations against %d, rows" % (tab, n_a, n_it - n_a, n_it), bits([torch.cat([ra, rb])]), bits([rows]))

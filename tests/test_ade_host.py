@@ -133,7 +133,8 @@ def test_the_mixture_and_its_quantile_nodes():
     # p(g) is the mean over the draws of the per-draw weights, not the weights of the mean curve
     class Two:
         def classes(self, ts, te, t0, n_bins):
-            return np.eye(n_bins, dtype=np.int64), np.ones(n_bins, dtype=np.int64), np.array([2 * n_bins, 0])
+            # (a death per birth bin, in the last bin: cells with jb + a < n_bins, as lr_ade_classes fills them)
+            return np.eye(n_bins, dtype=np.int64)[:, ::-1].copy(), np.ones(n_bins, dtype=np.int64), np.array([2 * n_bins, 0])
 
         def profile(self, dead, cens, mu, shapes):
             logk = np.log(np.asarray(shapes))

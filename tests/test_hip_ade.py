@@ -3,7 +3,7 @@ limit): the class counts with np.array_equal against the numpy restatement on li
 trip, bin counts on both sides of the LDS table's limit, year-resolution and continuous times, the edge lineages, and a
 second call on dirty outputs; the profile against the restatement within 1e-9 of the sum of the absolute class terms (c^
 within 1e-7 relative) on the smallest and the largest tables, with more classes than the threads keep in registers, under
-rates scaled by 1e-12 and 1e6, scale invariance on the device itself, the same bits from a second call; the two degenerate
+rates scaled by 1e-12 and 1e6, scale invariance on the device itself, the same bits from a second call; counts beyond 32 bits, exactly 2^28 times the table's own result; the two degenerate
 cases; flagged draws and bad shapes beside good ones; every argument error; the buffer contract on exact-size guarded
 buffers; fit_rates on the device against fit_rates on the restatement; and the three command lines end to end, with the
 other post-run flags' files byte-identical beside --ade and without it."""
@@ -43,6 +43,10 @@ def test_the_classes_equal_the_restatement_and_again_on_dirty_outputs():
 @pytest.mark.parametrize("group", ["small", "scaled", "large"])
 def test_the_profile_against_the_restatement_and_again_on_dirty_outputs(group):
     run_case("profile", group)
+
+
+def test_counts_beyond_32_bits_scale_the_profile_exactly():
+    run_case("big_counts")
 
 
 def test_no_deaths_and_no_finite_maximiser():
