@@ -646,6 +646,13 @@ int lr_mcmc_p4_config(const lr_engine* e, int32_t* word /* host */);
  * every other kernel and under the environment variable LR_P4_RESIDENT=0, read by lr_mcmc_init / lr_mcmc_restore, which
  * sends every trip through the scan loop. */
 int lr_mcmc_p4_resident(const lr_engine* e, int32_t out[4] /* host */);
+/* measurement hook: a wave of that kernel that runs all its resident trips takes them as one block of straight-line code,
+ * without the test and branch per trip (no gather is requested sooner than in the trip-by-trip form); the same results
+ * bit for bit.  out[0] = 1 when that form runs, and the waves that take the block: out[1] of the ten scanner waves, out[2]
+ * of the two scanner waves that also make the draws ahead, out[3] of the two helper waves; all zero for every other
+ * kernel, without resident groups and under the environment variable LR_P4_PIPE=0, read where LR_P4_RESIDENT is, which
+ * runs the resident trips one by one on every wave. */
+int lr_mcmc_p4_pipe(const lr_engine* e, int32_t out[4] /* host */);
 int lr_mcmc_destroy(lr_engine* e);
 
 #ifdef __cplusplus

@@ -526,8 +526,14 @@ __global__ __launch_bounds__(T, LR_PERSIST_MINWAVES) void lr_persist_kernel(
 #define LR_P4_NR_DRAW 4       /* ... per lane of the two scanner waves that also make the draws ahead (waves 4, 5) */
 #endif
 #define LR_P4_RES_HELP 5      /* resident trips per helper lane: every trip lr_set_shares' rule gives the helpers */
+// PIPE (NR > 0 only): 1 = a wave that runs all its resident trips takes them as one basic block without the scalar test
+// and branch per trip (lr_resident_trips_block, lr_scan.h): the same operations on every accumulator in the same order,
+// every gather where the trip-by-trip form has it.  The launch picks between 0 and LR_P4_PIPE (lr_p4_pipe_choice).
+#ifndef LR_P4_PIPE
+#define LR_P4_PIPE 1          /* 0: the one-block form is not built */
+#endif
 template <int H, bool GENERAL, bool PARAM /* a parametric sampler's chain step (DDRate, trend_rate) instead of the RJ sampler's */,
-          bool HELP = false, int CFG = LR_P4_CFG_GENERIC, int NR = 0>
+          bool HELP = false, int CFG = LR_P4_CFG_GENERIC, int NR = 0, int PIPE = 0>
 __global__ __launch_bounds__(LR_P4_THREADS, LR_P4_THREADS / 256) void lr_persist4_kernel(const lr_step_args* __restrict__ ap /* in global memory: a by-value argument struct measured
                                                                        0.2 us per launch faster, but one instantiation then kept a copy of it in scratch
                                                                        memory and read its fields from there in every phase */,
@@ -536,6 +542,7 @@ __global__ __launch_bounds__(LR_P4_THREADS, LR_P4_THREADS / 256) void lr_persist
     static_assert(!HELP || (!GENERAL && !PARAM), "helper waves: RJ sampler at unit resolution");
     static_assert(CFG == LR_P4_CFG_GENERIC || (HELP && H <= 264), "a configuration word comes with the helper waves");
     static_assert(NR == 0 || HELP, "resident groups come with the helper waves");
+    static_assert(PIPE == 0 || (PIPE == 1 && NR > 0), "the one-block form is one of the resident trips");
     const lr_step_args& a = *ap;
     LR_PSTAMP(0);      // entry (LR_DIAG: wall-clock stamps of a launch's stages, blocks < 64; scratch/diag_p4_launch.py)
     constexpr int NW = LR_P4_THREADS / LR_WAVE;          // 16 waves: 2 steppers + 14 scanners (HELP: 2 + 2 helpers + 12)
@@ -704,7 +711,7 @@ __global__ __launch_bounds__(LR_P4_THREADS, LR_P4_THREADS / 256) void lr_persist
         if (decltype(resident_)::value) {
             // (trips behind the resident ones - LR_P4_HELP_TRIPS above LR_P4_RES_HELP - as before)
             const long long done = (long long)hres.trips * (2 * LR_WAVE);
-            lr_resident_trips(reinterpret_cast<const char*>(tab[pr]), hres, s0, s1);
+            lr_resident_trips<LR_P4_RES_HELP, HDR, (PIPE > 0)>(reinterpret_cast<const char*>(tab[pr]), hres, s0, s1);
             if (nh > done) lr_persist_scan<H, GENERAL, 1, false, false>(reinterpret_cast<const char*>(tab[pr]), pk, done, nh - done, tid - 2 * LR_WAVE, 2 * LR_WAVE, &s0, &s1);
         } else if (nh > 0) lr_persist_scan<H, GENERAL, 1, false, false>(reinterpret_cast<const char*>(tab[pr]), pk, 0, nh, tid - 2 * LR_WAVE, 2 * LR_WAVE, &s0, &s1);
         leave_sums(pr, s0, s1);
@@ -712,7 +719,7 @@ __global__ __launch_bounds__(LR_P4_THREADS, LR_P4_THREADS / 256) void lr_persist
     // NR > 0: a scanner wave's share of the scan for pair `pr` (a compile-time constant here too)
     auto scan_resident = [&](auto pr_, double* s0, double* s1, lr_scan_tail* tail) {
         constexpr int pr = decltype(pr_)::value;
-        lr_persist_scan_pair_resident(reinterpret_cast<const char*>(tab[pr]), pk.idx8 + nh, n8w, sid, LR_P4_SCANNERS, res, s0, s1, tail);
+        lr_persist_scan_pair_resident<(PIPE > 0)>(reinterpret_cast<const char*>(tab[pr]), pk.idx8 + nh, n8w, sid, LR_P4_SCANNERS, res, s0, s1, tail);
     };
     // prologue: pair 0's pending proposal is scanned so that phase A can step it - unless the launch before this one has
     // left the sums of that very scan (its last phase scored pair 0; lr_prepare_constants clears the flag whenever the
@@ -760,7 +767,7 @@ __global__ __launch_bounds__(LR_P4_THREADS, LR_P4_THREADS / 256) void lr_persist
             }
         }
     } else if (!scanner)
-        lr_persist4_steppers<(H <= 264 ? lr_bins_per_lane(H) : 0), ES, NW, PARAM ? 1 : 0, HELP, CFG, NR>(
+        lr_persist4_steppers<(H <= 264 ? lr_bins_per_lane(H) : 0), ES, NW, PARAM ? 1 : 0, HELP, CFG, NR + 64 * PIPE>(
             (const __attribute__((address_space(3))) lr_step_args*)&a_lds, c0, C, wave, lane,
             (__attribute__((address_space(3))) lr_seg_scratch*)&scratch[wave], (lr_lds_f64*)&st_f64[0][0], (lr_lds_i32*)&st_i32[0][0],
             (lr_lds_f64*)&red[0][0][0], (lr_lds_f64*)reinterpret_cast<double*>(tab[0]), 2 * LR_UNIT_PLANES * H,
@@ -809,8 +816,8 @@ __global__ __launch_bounds__(LR_P4_THREADS, LR_P4_THREADS / 256) void lr_persist
                 double s0 = 0.0, s1 = 0.0;
                 lr_scan_tail tail;
                 if constexpr (NRD > 0) {
-                    if (ph == 0) lr_persist_scan_pair_resident(reinterpret_cast<const char*>(tab[1]), pk.idx8 + nh, n8w, sid, LR_P4_SCANNERS, dres, &s0, &s1, &tail);
-                    else lr_persist_scan_pair_resident(reinterpret_cast<const char*>(tab[0]), pk.idx8 + nh, n8w, sid, LR_P4_SCANNERS, dres, &s0, &s1, &tail);
+                    if (ph == 0) lr_persist_scan_pair_resident<(PIPE > 0)>(reinterpret_cast<const char*>(tab[1]), pk.idx8 + nh, n8w, sid, LR_P4_SCANNERS, dres, &s0, &s1, &tail);
+                    else lr_persist_scan_pair_resident<(PIPE > 0)>(reinterpret_cast<const char*>(tab[0]), pk.idx8 + nh, n8w, sid, LR_P4_SCANNERS, dres, &s0, &s1, &tail);
                 } else
                 lr_persist_scan<H, GENERAL, 1, false, true>(reinterpret_cast<const char*>(tab[1 - ph]), pk, nh, n8w, sid, LR_P4_SCANNERS, &s0, &s1, nullptr, &tail);
                 leave_sums(1 - ph, s0, s1);
@@ -975,6 +982,7 @@ extern "C" int lr_mcmc_create(const lr_mcmc_config* cfg, const double* ts, const
     e->p4_help = lr_p4_help_choice(e);                  // (lr_mcmc_describe before init; latched again by lr_set_shares)
     e->p4_cfg = lr_p4_cfg_choice(e);
     e->p4_resident = lr_p4_resident_choice(e);
+    e->p4_pipe = lr_p4_pipe_choice(e);
     e->streaming = false;
     e->packed_scan = plan.packed_scan;
     e->fork = nullptr;
@@ -1334,6 +1342,12 @@ extern "C" int lr_mcmc_steps(lr_engine* e, int64_t n_iters, void* stream_) {
         if (general && param) hipLaunchKernelGGL((lr_persist4_kernel<HH, true, true>), g4, b4, 0, stream, ap, pk, e->n8, e->p4, (long long)n, p4_carry);   \
         else if (general) hipLaunchKernelGGL((lr_persist4_kernel<HH, true, false>), g4, b4, 0, stream, ap, pk, e->n8, e->p4, (long long)n, p4_carry);      \
         else if (param) hipLaunchKernelGGL((lr_persist4_kernel<HH, false, true>), g4, b4, 0, stream, ap, pk, e->n8, e->p4, (long long)n, p4_carry);        \
+        else if (LR_P4_NR > 0 && LR_P4_PIPE > 0 && e->p4_help && e->p4_resident && e->p4_pipe && e->p4_cfg == LR_P4_CFG_BDI)   /* (resident trips as one block: lr_p4_pipe_choice) */ \
+            hipLaunchKernelGGL((lr_persist4_kernel<(HH <= 264 ? HH : 264), false, false, true, LR_P4_CFG_BDI, LR_P4_NR, LR_P4_PIPE>), g4, b4, 0, stream, ap, pk, e->n8, e->p4, (long long)n, p4_carry); \
+        else if (LR_P4_NR > 0 && LR_P4_PIPE > 0 && e->p4_help && e->p4_resident && e->p4_pipe && e->p4_cfg == LR_P4_CFG_KEIDING)                                  \
+            hipLaunchKernelGGL((lr_persist4_kernel<(HH <= 264 ? HH : 264), false, false, true, LR_P4_CFG_KEIDING, LR_P4_NR, LR_P4_PIPE>), g4, b4, 0, stream, ap, pk, e->n8, e->p4, (long long)n, p4_carry); \
+        else if (LR_P4_NR > 0 && LR_P4_PIPE > 0 && e->p4_help && e->p4_resident && e->p4_pipe)                                                                    \
+            hipLaunchKernelGGL((lr_persist4_kernel<(HH <= 264 ? HH : 264), false, false, true, LR_P4_CFG_GENERIC, LR_P4_NR, LR_P4_PIPE>), g4, b4, 0, stream, ap, pk, e->n8, e->p4, (long long)n, p4_carry); \
         else if (LR_P4_NR > 0 && e->p4_help && e->p4_resident && e->p4_cfg == LR_P4_CFG_BDI)   /* (resident groups: lr_p4_resident_choice) */ \
             hipLaunchKernelGGL((lr_persist4_kernel<(HH <= 264 ? HH : 264), false, false, true, LR_P4_CFG_BDI, LR_P4_NR>), g4, b4, 0, stream, ap, pk, e->n8, e->p4, (long long)n, p4_carry); \
         else if (LR_P4_NR > 0 && e->p4_help && e->p4_resident && e->p4_cfg == LR_P4_CFG_KEIDING)                                              \
@@ -1452,6 +1466,27 @@ extern "C" int lr_mcmc_p4_resident(const lr_engine* e, int32_t* out) {
     out[1] = on ? (int32_t)(h < LR_P4_RES_HELP ? h : LR_P4_RES_HELP) : 0;
     out[2] = (int32_t)e->n8;
     out[3] = (int32_t)h;
+    return LR_OK;
+}
+
+// the four-chain kernel's one-block form of the resident trips in use (lr_resident_trips_block; all zero under
+// LR_P4_PIPE=0, without resident groups and for every other kernel): out = 1, and how many waves run all their resident
+// trips and so take the block - of the ten scanner waves 6..15, of the two waves 4, 5 with the draw duty, of the two helper
+// waves.  The counts are worked out HERE, on the host, the way lr_resident_load works out r.trips on the device, for the
+// equal shares that the helper form has (lr_set_shares gives it no others: n8w = n8 - nh in the kernel); should that form
+// ever get unequal shares (lr_p4_shares.delta), a wave's end is k_mine x 768 and this must follow.
+extern "C" int lr_mcmc_p4_pipe(const lr_engine* e, int32_t* out) {
+    if (!e || !out) return LR_ERR_NULL;
+    out[0] = out[1] = out[2] = out[3] = 0;
+    if (!(e->plan.family == 2 && e->p4_help && e->p4_resident && e->p4_pipe && LR_P4_NR > 0 && LR_P4_PIPE > 0)) return LR_OK;
+    const long long h = e->p4.help_trips, n = e->n8 - h * 128;
+    out[0] = 1;
+    for (int q = 0; q < 12; ++q) {          // scanner wave 4 + q: the trips k with 64 q + 768 k < n (lr_resident_load)
+        const long long mine = 64 * q < n ? (n - 64 * q + 767) / 768 : 0;
+        if (q < 2) out[2] += mine >= LR_P4_NR_DRAW;
+        else out[1] += mine >= LR_P4_NR;
+    }
+    out[3] = h >= LR_P4_RES_HELP ? 2 : 0;
     return LR_OK;
 }
 

@@ -816,9 +816,65 @@ __device__ __forceinline__ void lr_resident_load(lr_resident_groups<NR, HDR>& r,
 
 // the resident trips of one scan against the pair table at `lbase`: per trip the operations of lr_persist_scan_pair's loop
 // body on the same values, in trip order
+// BLOCK: a wave that runs all its NR resident trips (one scalar test: r.trips is wave-uniform and constant for the launch)
+// takes them as ONE basic block (lr_resident_trips_block), without the scalar test and branch per trip; a wave with fewer
+// trips runs the loop below.
+// The block: per trip the eight gathers in the order of their use (E0 .. E6, S: LDS reads of a wave return in order, the
+// compiler counts the waits), then the two chains' trees in lock step - eight steps of one fp64 instruction per chain.
+// Every accumulator sees the operations of the loop below on the same values in the same order.  The scheduling groups
+// (one DS read each; two VALU instructions per step, three with the count's conversion) hold the scheduler to the written
+// order: every gather of trip k + 1 stands behind the last addition of trip k, as in the loop.  Left to itself the
+// scheduler requests two or three gathers of the next trip early, and every gather requested early measured slower
+// (the four-chain kernel).  The two header masks are asm, as in the loop.
 template <int NR, bool HDR>
+__device__ __forceinline__ void lr_resident_trips_block(const char* __restrict__ lbase, const lr_resident_groups<NR, HDR>& r,
+                                                        double& acc0, double& acc1) {
+#pragma unroll
+    for (int k = 0; k < NR; ++k) {
+        double2 E[LR_SLOTS];
+#pragma unroll
+        for (int j = 0; j < LR_SLOTS; ++j) {
+            E[j] = *reinterpret_cast<const double2*>(lbase + r.o[k][j]);
+            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);      // one DS read
+        }
+        unsigned int oS = r.hd[k], c4 = 0u;
+        if (!HDR) {
+            asm volatile("v_and_b32_e32 %0, 0xfff0, %1" : "=v"(oS) : "v"(r.hd[k]));
+            asm volatile("v_and_b32_e32 %0, 15, %1" : "=v"(c4) : "v"(r.hd[k]));
+        }
+        const double2 S = *reinterpret_cast<const double2*>(lbase + oS);
+        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+        const double cnt = HDR ? r.cnt[k] : (double)c4;
+        // the fixed pairwise tree over the slots, then the birth entry `count` times; a scheduling group of VALU
+        // instructions per step
+        const double a0 = E[0].x + E[1].x, a1 = E[0].y + E[1].y;
+        __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
+        const double b0 = E[2].x + E[3].x, b1 = E[2].y + E[3].y;
+        __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
+        const double c0 = a0 + b0, c1 = a1 + b1;
+        __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
+        const double d0 = E[4].x + E[5].x, d1 = E[4].y + E[5].y;
+        __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
+        const double e0 = d0 + E[6].x, e1 = d1 + E[6].y;
+        __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
+        const double u0 = c0 + e0, u1 = c1 + e1;
+        __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
+        const double f0 = fma(cnt, S.x, u0), f1 = fma(cnt, S.y, u1);
+        __builtin_amdgcn_sched_group_barrier(0x002, 3, 0);          // (and the count's conversion)
+        acc0 += f0, acc1 += f1;
+        __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
+    }
+}
+
+template <int NR, bool HDR, bool BLOCK = false>
 __device__ __forceinline__ void lr_resident_trips(const char* __restrict__ lbase, const lr_resident_groups<NR, HDR>& r,
                                                   double& acc0, double& acc1) {
+    if constexpr (BLOCK) {
+        if (r.trips == NR) {
+            lr_resident_trips_block<NR, HDR>(lbase, r, acc0, acc1);
+            return;
+        }
+    }
 #pragma unroll
     for (int k = 0; k < NR; ++k) {
         if (k >= r.trips) break;
@@ -846,7 +902,7 @@ __device__ __forceinline__ void lr_resident_trips(const char* __restrict__ lbase
 // lr_persist_scan_pair<H, 1, true> (hand-placed loads, the wave's own trip count) with the first r.trips trips resident:
 // the loop starts at trip r.trips - its first group is requested before the resident trips and has landed behind them -
 // and runs no trip at all for a wave whose trips are all resident (r.trips < NR: the wave has no more).
-template <int NR, bool HDR>
+template <bool BLOCK = false, int NR, bool HDR>
 __device__ __forceinline__ void lr_persist_scan_pair_resident(const char* __restrict__ lbase, const uint4* __restrict__ idx8,
                                                               long long n8, long long sid, int n_scan,
                                                               const lr_resident_groups<NR, HDR>& r, double* acc0_,
@@ -862,7 +918,7 @@ __device__ __forceinline__ void lr_persist_scan_pair_resident(const char* __rest
     // (unconditionally, as every load of the loop: a wave without a trip left requests a group - or zeros of the spare -
     // that it will not score)
     lr_gload16_async(w, gbase, off);
-    lr_resident_trips(lbase, r, acc0, acc1);
+    lr_resident_trips<NR, HDR, BLOCK>(lbase, r, acc0, acc1);
     while (has) {
         lr_gload_wait<0>(w);
         const unsigned int oS = w.x & 0xfff0u;

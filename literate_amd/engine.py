@@ -271,6 +271,14 @@ class ChainEngine:
         _hip.check(self.lib.lr_mcmc_p4_resident(self.handle, out), "lr_mcmc_p4_resident")
         return tuple(int(v) for v in out)
 
+    def p4_pipe(self):
+        """One-block form of the resident trips in the four-chain kernel steps() runs: (1 when it runs, waves that run all
+        their resident trips and so take the block among the ten scanner waves, among the two with the draw duty, among
+        the two helper waves); all zero for another kernel, without resident trips or with LR_P4_PIPE=0 at init()."""
+        out = (C.c_int32 * 4)()
+        _hip.check(self.lib.lr_mcmc_p4_pipe(self.handle, out), "lr_mcmc_p4_pipe")
+        return tuple(int(v) for v in out)
+
     def timed_steps(self, n):
         """steps(n) bracketed by HIP events on the launch stream; returns elapsed device ms (blocks)."""
         ms = C.c_float(0.0)
