@@ -1,5 +1,5 @@
 """ctypes binding of libliterate_hip.so (include/literate_hip.h, include/literate_hip_age.h, include/literate_hip_ade.h,
-include/literate_hip_adej.h, include/literate_hip_mlik.h).  Fails loudly: no fallback."""
+include/literate_hip_adej.h, include/literate_hip_mlik.h, include/literate_hip_tmlik.h).  Fails loudly: no fallback."""
 import ctypes as C
 import os
 
@@ -15,6 +15,7 @@ LR_KMAX, LR_ROW, LR_MAX_BINS = 32, 64, 4094
 LR_ADE_MAX_BINS = 512      # lr_ade_classes, lr_ade_profile (include/literate_hip_ade.h)
 LR_ADEJ_MAX_BINS, LR_ADEJ_MOVES, LR_ADEJ_STATE_W, LR_ADEJ_ROW_W = 128, 5, 96, 73      # include/literate_hip_adej.h
 LR_MLIK_MAX_BINS, LR_MLIK_MAX_TEMPS, LR_MLIK_MOVES, LR_MLIK_STATE_W, LR_MLIK_ROW_W = 512, 128, 2, 16, 12      # include/literate_hip_mlik.h
+LR_TMLIK_MAX_BINS, LR_TMLIK_MAX_TEMPS, LR_TMLIK_MAX_MODELS, LR_TMLIK_MOVES, LR_TMLIK_STATE_W, LR_TMLIK_ROW_W = 512, 128, 64, 2, 16, 12      # include/literate_hip_tmlik.h
 LR_WARN_KCAP = 2
 LR_STATE_ROWS, LR_ISTATE_ROWS = 9, 5
 LR_TRACE_HEAD = 13
@@ -50,8 +51,16 @@ class McmcLayout(C.Structure):
                 ("spec_chains_per_team", c_i32), ("streaming", c_i32), ("packed_scan", c_i32), ("reserved3", c_i32)]
 
 
+class TmlikProblem(C.Structure):
+    """lr_tmlik_problem (include/literate_hip_tmlik.h): the descriptor both lr_tmlik_* entry points take; the stream rides in it"""
+    _fields_ = [("n_spec", c_vp), ("n_exti", c_vp), ("DT", c_vp), ("trends", c_vp), ("wins", c_vp), ("state", c_vp),
+                ("betas", c_vp), ("scales", c_vp), ("col", c_vp), ("flags", c_vp), ("key0", c_vp),
+                ("n_bins", c_i32), ("n_cols", c_i32), ("n_models", c_i32), ("n_reps", c_i32), ("T", c_i32),
+                ("seed", C.c_uint64), ("stream", c_vp)]
+
+
 # name -> (restype, argtypes); exactly the symbols include/literate_hip.h, literate_hip_age.h, literate_hip_ade.h and
-# literate_hip_adej.h, literate_hip_mlik.h declare (+ the RNG debug hook)
+# literate_hip_adej.h, literate_hip_mlik.h, literate_hip_tmlik.h declare (+ the RNG debug hook)
 SIGNATURES = {
     "lr_version": (c_i32, []),
     "lr_bin_events_workspace_bytes": (c_i64, [c_i64, c_i32]),
@@ -109,6 +118,8 @@ SIGNATURES = {
     "lr_mlik_steps": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_f64, c_f64, c_i32, c_i32, c_f64, c_vp, c_vp, c_i32, C.c_uint64, c_i32, c_i32,
                               c_vp, c_i64, c_i64, c_i32, c_vp, c_i64, c_vp]),
     "lr_mlik_estimate": (c_i32, [c_vp, c_i64, c_i32, c_i32, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "lr_tmlik_init": (c_i32, [C.POINTER(TmlikProblem)]),
+    "lr_tmlik_steps": (c_i32, [C.POINTER(TmlikProblem), c_i64, c_i64, c_i32, c_vp, c_i64, c_i64]),
     "lr_ess_summary_workspace_bytes": (c_i64, [c_i32, c_i32, c_i32, c_vp, c_i32, c_f64, c_i32]),
     "lr_ess_summary": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_i32, c_f64, c_i32, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
     "lr_col_summary_workspace_bytes": (c_i64, [c_i32, c_i32, c_i32, c_vp, c_i32, c_f64, c_i32, c_i32]),
@@ -190,3 +201,12 @@ def launch(fn, device, *args):
     import torch
     with torch.cuda.device(device):
         return fn(*args, stream_ptr(device))
+
+
+def launch_problem(fn, device, problem, *args):
+    """Call an entry point that takes a descriptor with the stream in it (lr_tmlik_*): `device`'s current torch stream is put
+    into problem.stream, `device` made current for the call."""
+    import torch
+    with torch.cuda.device(device):
+        problem.stream = stream_ptr(device)
+        return fn(C.byref(problem), *args)

@@ -158,6 +158,7 @@ struct lr_trend_params {
 };
 
 // likelihood_function's rate half for ONE bin (trend_rate.py:73-88); t = TREND[b]
+// (lr_trend_bin_rates_log at the end of this file is the same map from lr_log(t): change the two together)
 __device__ __forceinline__ void lr_trend_bin_rates(const lr_trend_params& p, double t, int const_birth, int const_death,
                                                    double* br_, double* dr_) {
     // TREND ** exponent through lr_pow_of_log, one logarithm for both processes (TREND is in (0, 1])
@@ -209,4 +210,20 @@ __device__ __forceinline__ double lr_trend_prior(double v, int lane) {
     if (lane == 4 || lane == 5) t = (y <= 0.0) ? -INFINITY : 2.0 * ly - y - LOG2 + LOG2;   // - lgamma(3) - log(.5)
     if (lane >= LR_TR_NPAR) t = 0.0;
     return lr_wave_sum(t);
+}
+
+// lr_trend_bin_rates from lt = lr_log(TREND[b]) - the same expressions, for a caller that keeps the covariate's logarithm
+// (lr_tmlik.hip takes it once per launch, not once per iteration); lt is not read when both processes are constant
+__device__ __forceinline__ void lr_trend_bin_rates_log(const lr_trend_params& p, double lt, int const_birth, int const_death,
+                                                       double* br_, double* dr_) {
+    double br = 1.0 * p.l_min, dr = 1.0 * p.m_min;
+    if (!const_birth) {
+        br = p.l_min + p.alpha * lr_pow_of_log(lt, p.delta);
+        if (br <= 0.0) br = LR_DD_SMALL;
+    }
+    if (!const_death) {
+        dr = p.m_min + p.beta * lr_pow_of_log(lt, p.gamma);
+        if (dr <= 0.0) dr = LR_DD_SMALL;
+    }
+    *br_ = br, *dr_ = dr;
 }

@@ -19,9 +19,10 @@ is uniform on its reflected range [0, present) with the prior's cut at origin + 
 that prior is normalised by construction and the value needs no constant.  Values of runs on the same data compare;
 compare A_MLIK.npz B_MLIK.npz refuses files of other data.
 
-Not built: trend_rate.py (its additive window of 0.001 against a Normal(0, 5) prior needs a window schedule of its own),
-LiteRateForward.py (its RJ sampler already averages over its models), swaps between temperatures, several GPUs (rank 0
-carries every chain).
+trend_rate.py's models have a module of their own (literate_amd/trend_mlik.py: a grid of models per launch, the additive
+window tuned during the burn-in); its <stem>_MLIK.npz holds several models and the tool below expands it into one row each.
+Not built: LiteRateForward.py (its RJ sampler already averages over its models), swaps between temperatures, several GPUs
+(rank 0 carries every chain).
 
     python -m literate_amd.mlik A_MLIK.npz B_MLIK.npz [-o table.tsv]
 """
@@ -184,11 +185,16 @@ def write_run(eng, rank, burnin, temps, reps, n_iter, s_freq, alpha, widen, seed
 # ---- the comparison tool -----------------------------------------------------------------------------------------------
 def compare(paths):
     """Rows (dicts, COMPARE_HEAD) of <stem>_MLIK.npz files sorted by log Z, best first; two_ln_bf = 2 (logZ - logZ of the
-    best), its standard error from the two replicate standard errors.  Files of other data (fingerprints) are refused."""
+    best), its standard error from the two replicate standard errors.  A file of several models (trend_rate.py --mlik) gives
+    a row per model.  Files of other data (fingerprints) are refused."""
     from .waic import fingerprint_mismatch
     items = []
     for p in paths:
         with np.load(p) as z:
+            if np.ndim(z["logZ_ss"]) == 1:          # a file of several models (trend_mlik.write_tables): one row each
+                for name, lz, se in zip(z["names"], z["logZ_ss"], z["logZ_ss_se"]):
+                    items.append(dict(name=p, model=str(name), logZ_ss=float(lz), logZ_ss_se=float(se), fp=np.asarray(z["fingerprint"])))
+                continue
             items.append(dict(name=p, model=str(z["model"]), logZ_ss=float(z["logZ_ss"]), logZ_ss_se=float(z["logZ_ss_se"]),
                               fp=np.asarray(z["fingerprint"])))
     for it in items[1:]:

@@ -1021,6 +1021,110 @@ def mlik_estimate(rows, betas, row0=0, n_rows=None, out=None):
     return MlikEstimate(*res)
 
 
+TMLIK_ROW = ("it", "beta", "lik", "prior", "l_min", "m_min", "alpha", "beta_slope", "delta", "gamma", "win", "model")
+TMLIK_STATE = {"args": 0, "lik": 6, "prior": 7, "proposed": 8, "accepted": 10, "beta": 12, "scale": 13, "win": 14, "model": 15}
+
+
+class TmlikData:
+    """The statistics the trend likelihood is a function of (create_bins' N_SPEC, N_EXTI, DT [n_bins]) and the normalised
+    covariates trends [n_cols, n_bins], as float64 device tensors: what every lr_tmlik_* call of one run shares."""
+
+    def __init__(self, n_spec, n_exti, DT, trends, device=None):
+        torch = _torch()
+        self.n_spec = _dev(n_spec, torch.float64, device).reshape(-1)
+        self.device = self.n_spec.device
+        self.n_exti = _dev(n_exti, torch.float64, self.device).reshape(-1)
+        self.DT = _dev(DT, torch.float64, self.device).reshape(-1)
+        self.trends = _dev(trends, torch.float64, self.device)
+        if self.trends.dim() == 1:
+            self.trends = self.trends.reshape(1, -1)
+        self.n_bins = int(self.DT.numel())
+        if self.n_exti.numel() != self.n_bins or self.n_spec.numel() != self.n_bins or self.trends.dim() != 2 \
+                or self.trends.shape[1] != self.n_bins:
+            raise ValueError("shape mismatch: n_spec, n_exti, DT [n_bins]; trends [n_cols, n_bins]")
+        self.n_cols = int(self.trends.shape[0])
+
+
+class TmlikGrid:
+    """The chain grid of one run of lr_tmlik_*: the models (col, flags: bit 0 const_B, bit 1 const_D, key0) [M], the ladder
+    betas, scales [T] - host arrays that travel in the kernel arguments - and the replicates."""
+
+    def __init__(self, col, flags, key0, betas, scales, n_reps):
+        self.col = np.ascontiguousarray(np.asarray(col, dtype=np.int32).ravel())
+        self.flags = np.ascontiguousarray(np.asarray(flags, dtype=np.int32).ravel())
+        self.key0 = np.ascontiguousarray(np.asarray(key0, dtype=np.int64).ravel())
+        self.betas, self.scales = _mlik_temps(betas, scales)
+        if self.flags.size != self.col.size or self.key0.size != self.col.size:
+            raise ValueError("shape mismatch: col, flags, key0 [M]")
+        self.M, self.T, self.R = int(self.col.size), int(self.betas.size), int(n_reps)
+
+    def part(self, models=None, reps=None):
+        """the grid of models [a, b) and / or replicates [a, b) of this one: the same chains, by key0"""
+        ma, mb = models if models is not None else (0, self.M)
+        ra, rb = reps if reps is not None else (0, self.R)
+        return TmlikGrid(self.col[ma:mb], self.flags[ma:mb], self.key0[ma:mb] + ra, self.betas, self.scales, rb - ra)
+
+
+def tmlik_problem(data, grid, wins, state, seed):
+    """The descriptor of a call (_hip.TmlikProblem; it refers to the arrays of data, grid, wins and state: keep them alive
+    while it is used).  wins [M, T], state [M, R, T, LR_TMLIK_STATE_W]: float64 device tensors."""
+    vp = lambda a: a.ctypes.data_as(_hip.c_vp)
+    return _hip.TmlikProblem(_hip.ptr(data.n_spec), _hip.ptr(data.n_exti), _hip.ptr(data.DT), _hip.ptr(data.trends), _hip.ptr(wins),
+                             _hip.ptr(state), vp(grid.betas), vp(grid.scales), vp(grid.col), vp(grid.flags), vp(grid.key0),
+                             data.n_bins, data.n_cols, grid.M, grid.R, grid.T, int(seed) & 0xFFFFFFFFFFFFFFFF, None)
+
+
+def _tmlik_wins(data, grid, wins):
+    torch = _torch()
+    w = _dev(np.full((grid.M, grid.T), float(wins)) if np.isscalar(wins) else wins, torch.float64, data.device)
+    if tuple(w.shape) != (grid.M, grid.T):
+        raise ValueError("wins must be [models, T]")
+    return w
+
+
+def tmlik_init(data, grid, wins, seed, out=None):
+    """The initial state of every chain of the grid (lr_tmlik_init) -> state [M, R, T, LR_TMLIK_STATE_W] (slots: TMLIK_STATE).
+    wins: the additive windows [M, T] (a device tensor is used as it is; a number: that window everywhere)."""
+    torch = _torch()
+    lib = _hip.load()
+    w = _tmlik_wins(data, grid, wins)
+    (state,) = _ade_out(out, ((grid.M, max(grid.R, 0), grid.T, _hip.LR_TMLIK_STATE_W),), (torch.float64,), data.device, "(state,)")
+    rc = _hip.launch_problem(lib.lr_tmlik_init, data.device, tmlik_problem(data, grid, w, state, seed))
+    _hip.check(rc, "lr_tmlik_init")
+    return state
+
+
+def tmlik_steps(data, grid, wins, state, it0, n_iters, s_freq, seed, rows=None, slot0=0, out=None):
+    """Iterations it0 .. it0 + n_iters - 1 of every chain of `state` (updated in place; lr_tmlik_steps) -> rows [M, cap, R, T,
+    LR_TMLIK_ROW_W] (columns: TMLIK_ROW), models outermost: rows[m] is what mlik_estimate reads.  rows: an earlier call's
+    buffer to go on writing into at slot `slot0`; otherwise a fresh one of exactly the rows due."""
+    torch = _torch()
+    lib = _hip.load()
+    w = _tmlik_wins(data, grid, wins)
+    if state.dtype != torch.float64 or tuple(state.shape) != (grid.M, grid.R, grid.T, _hip.LR_TMLIK_STATE_W) \
+            or not state.is_contiguous() or state.device != data.device:
+        raise ValueError("state must be tmlik_init's [models, replicates, T, LR_TMLIK_STATE_W] float64 tensor on the data's device")
+    n = rows_due(it0, n_iters, s_freq) if int(s_freq) >= 1 and int(n_iters) >= 0 and int(it0) >= 0 else 0
+    if rows is None:
+        (rows,) = _ade_out(out, ((grid.M, max(n, 0), grid.R, grid.T, _hip.LR_TMLIK_ROW_W),), (torch.float64,), data.device, "(rows,)")
+    elif rows.dtype != torch.float64 or rows.dim() != 5 or not rows.is_contiguous() or rows.device != data.device \
+            or (rows.shape[0], rows.shape[2], rows.shape[3], rows.shape[4]) != (grid.M, grid.R, grid.T, _hip.LR_TMLIK_ROW_W):
+        raise ValueError("rows must be a [models, cap, replicates, T, LR_TMLIK_ROW_W] float64 tensor on the data's device")
+    rc = _hip.launch_problem(lib.lr_tmlik_steps, data.device, tmlik_problem(data, grid, w, state, seed), int(it0), int(n_iters),
+                             int(s_freq), _hip.ptr(rows) if rows.numel() else None, int(rows.shape[1]), int(slot0))
+    _hip.check(rc, "lr_tmlik_steps")
+    return rows
+
+
+def tmlik_run(data, grid, wins, n_iter, s_freq, seed):
+    """A whole run at fixed windows: lr_tmlik_init, then n_iter iterations in one launch -> (rows [M, n_iter / s_freq rounded
+    up, R, T, LR_TMLIK_ROW_W], state [M, R, T, LR_TMLIK_STATE_W]); device tensors."""
+    w = _tmlik_wins(data, grid, wins)
+    state = tmlik_init(data, grid, w, seed)
+    rows = tmlik_steps(data, grid, w, state, 0, n_iter, s_freq, seed)
+    return rows, state
+
+
 EssSummary = namedtuple("EssSummary", "mean ess act se_mean stop_lag pooled_mean pooled_ess rhat n")
 EssSummary.__doc__ = """lr_ess_summary's results.  mean, ess, act (in samples), se_mean float64 and stop_lag int32: [C, K] per chain and
 column; pooled_mean, pooled_ess, rhat: [K]; n: rows kept per chain.  ESS and ACT are NaN, SE 0 and the stop lag 0 where a

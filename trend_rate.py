@@ -79,6 +79,27 @@ def build_parser():
                    'chain), every lineage\'s draws sorted, fitted and smoothed on the GPU; rank runs of the same program on '
                    'the same data with `python -m literate_amd.loo A_LOO_pointwise.npz B_LOO_pointwise.npz`; not with -rm_first_bin 1 (extension)')
     p.add_argument('--loo_draws', type=int, default=1000, help='posterior draws PSIS-LOO is computed from (2 to 8192)')
+    p.add_argument('--mlik', type=float, default=-1.0, help='after the run, write <stem>_MLIK.tsv, <stem>_MLIK_temps.tsv and <stem>_MLIK.npz '
+                   'beside the logs: the marginal likelihood log Z of the trend models (stepping stones, with the trapezoid '
+                   'thermodynamic integration) over --mlik_temps power posteriors x --mlik_reps replicates, chains of their own '
+                   'on the run\'s per-bin statistics and seed, this burn-in fraction of their rows dropped; the constant-rate model '
+                   '_CONB_COND is always among the models and every other one gets 2 ln BF against it; the additive window on '
+                   'the slopes is tuned per temperature during the burn-in (0: the reference\'s 0.001 at every temperature, '
+                   'which cannot sample the priors: the estimate is then not to be trusted); the additive acceptance in the files is that of the '
+                   'steps that move a slope (a step that fires for neither slope is always accepted and is not counted, so it is not the '
+                   'trend log\'s raw acceptance); files of several runs on the same '
+                   'data: `python -m literate_amd.mlik A_MLIK.npz B_MLIK.npz`; at most 512 time bins; one GPU (extension)')
+    p.add_argument('--mlik_columns', type=str, default='run', help='covariates screened: run (the run\'s -trend_index), all (every '
+                   'column of the trend file) or a comma-separated list of column indices; each normalised as the run\'s own')
+    p.add_argument('--mlik_models', type=str, default='run', help='models per column: run (the run\'s -const_B / -const_D '
+                   'combination) or all (EXPB_EXPD, EXPB_COND and CONB_EXPD)')
+    p.add_argument('--mlik_temps', type=int, default=16, help='temperatures of the ladder, beta_j = (j / (T - 1)) ** (1 / alpha)')
+    p.add_argument('--mlik_reps', type=int, default=8, help='independent replicates of the ladder (the standard error is theirs)')
+    p.add_argument('--mlik_n', type=int, default=0, help='iterations of the power-posterior chains (default: -n)')
+    p.add_argument('--mlik_s', type=int, default=0, help='their sampling frequency (default: -s)')
+    p.add_argument('--mlik_alpha', type=float, default=0.3, help='exponent of the temperature ladder')
+    p.add_argument('--mlik_widen', type=float, default=8.0, help='cap of the multiplier\'s window scale min(beta ** -1/2, widen) of the cold '
+                   'chains (1: the reference\'s window at every temperature)')
     p.add_argument('--block', type=int, default=0, help='iterations per device window (logs are flushed once per window; '
                    'default: -p rounded up to ~50000)')
     return p
@@ -126,6 +147,19 @@ def main(argv=None):
         err = loo_arg_error(args.loo, args.loo_draws, rm_first_bin=args.rm_first_bin)
         if err:
             raise SystemExit(err)
+    if args.mlik != -1.0:
+        from literate_amd import trend_mlik
+        err = trend_mlik.arg_error(args.mlik, args.mlik_temps, args.mlik_reps, args.mlik_n or args.n, args.mlik_s or args.s,
+                                   args.mlik_alpha, args.mlik_widen)
+        err = err or trend_mlik.selection_error(args.mlik_columns, args.mlik_models, args.trend_index)
+        if err:
+            raise SystemExit(err)
+        # what depends on the trend file (a column that is not there, a constant one) is refused now, on every rank, not after the run
+        try:
+            mlik_selection = trend_mlik.read_selection(args.trend_data, args.mlik_columns, args.mlik_models, args.trend_index, args.const_B,
+                                                       True if args.no_death else args.const_D, int(args.rm_first_bin))
+        except (ValueError, OSError) as e:
+            raise SystemExit("--mlik: %s" % e if not str(e).startswith("--mlik") else str(e))
     print("\n\n             TrendRate - 20190205 (MI355X engine)\n")
     import torch
     import torch.distributed as dist
@@ -217,6 +251,13 @@ def main(argv=None):
     if args.loo != -1.0 and n_samples:
         from literate_amd import loo
         loo.write_run(eng, n_local, args.chains, world, rank, args.loo, args.loo_draws, "%s_%s" % (stem, args.trend_index))
+    if args.mlik != -1.0:
+        from literate_amd import trend_mlik
+        try:
+            trend_mlik.write_run(eng, rank, mlik_selection, args.mlik, args.mlik_temps, args.mlik_reps, args.mlik_n or args.n,
+                                 args.mlik_s or args.s, args.mlik_alpha, args.mlik_widen, seed, "%s_%s" % (stem, args.trend_index))
+        except ValueError as e:
+            raise SystemExit(str(e))
     eng.close()
     if world > 1:
         dist.barrier()
