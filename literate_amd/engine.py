@@ -25,7 +25,14 @@ class ChainEngine:
         dd: None = the runMCMC sampler (LRF:216-373); dict(m_birth, m_death, present, init_death) = the DDRate.py
         sampler (DD:124-241) on create_bins statistics: stats = (ORIGIN, N_TIME_BINS, DT), model 2;
         dict(kind="trend", m_birth=const_B, m_death=const_D) = the trend_rate.py sampler with
-        stats = (ORIGIN, N_TIME_BINS, TREND)."""
+        stats = (ORIGIN, N_TIME_BINS, TREND).
+        engine: "auto" lets the planner choose; any other value asks for a kernel family, and a request the chain count
+        (or the configuration) does not allow runs another family without an error - `layout.persistent` (1 two-chain,
+        2 four-chain, 3 speculative, 0 the launches; `layout.packed_scan`) and kernel_name() say what runs.
+        "persistent4" needs table groups of four chains: two chains at unit resolution run the two-chain kernel, and so
+        does a lone chain where it keeps unit tables (model 3, more than 254 bins).  "persistent2" runs the launches
+        for a lone chain on general tables and has no general-time form.  "spec" takes at most two chains per compute
+        unit (with team=k blocks and chains_per_team=cpb: cpb * (CUs // k) chains) and runs the launches beyond."""
         torch = _hip.require_gpu()
         self.lib = _hip.load()
         self.device = torch.device(device or "cuda")

@@ -15,6 +15,7 @@ The class rules below restate the code; tests/test_planner_map.py checks the pla
 configurations and derives the cell list from it, and tests/test_hip_edges.py runs every cell against the oracle.
 """
 import ctypes as C
+import functools
 import os
 import re
 
@@ -105,9 +106,11 @@ def engine_runs(engine, model, sampler, unit, n_bins):
     return engine in ("persistent4", "packed")
 
 
-def make_config(model, sampler, unit, n_bins, n_chains, n_lineages, engine_mode, frac_birth=0.0, frac_death=0.5):
+def make_config(model, sampler, unit, n_bins, n_chains, n_lineages, engine_mode, frac_birth=0.0, frac_death=0.5, team=0,
+                chains_per_team=0):
     """(frac_birth, frac_death): the shared in-bin fractions of unit-resolution data, (0, 0.5) for year-resolution input with
-    the default death_jitter; general times carry none."""
+    the default death_jitter; general times carry none.  (team, chains_per_team): ChainEngine's request for the
+    speculative kernel's team of blocks and its chains per team, 0 = the planner's choice."""
     from literate_amd import _hip
     end = float(n_bins) + 0.5
     return _hip.McmcConfig(
@@ -115,14 +118,17 @@ def make_config(model, sampler, unit, n_bins, n_chains, n_lineages, engine_mode,
         s_freq=10, n_trace_slots=4, update_fraction=0.75, t0=0.0, start_time=0.0, end_time=end, seed=1,
         unit_resolution=int(unit), engine_mode=int(engine_mode), frac_birth=float(frac_birth) if unit else 0.0,
         frac_death=float(frac_death) if unit else 0.0, sampler=int(sampler), m_birth=2 if sampler == 1 else 0,
-        m_death=2 if sampler == 1 else 0, dd_present=end if sampler == 1 else 0.0, dd_init_death=0.1)
+        m_death=2 if sampler == 1 else 0, team_request=int(team) | (int(chains_per_team) << 8),
+        dd_present=end if sampler == 1 else 0.0, dd_init_death=0.1)
 
 
-def query(model, sampler, unit, n_bins, n_chains, n_lineages, engine_mode, cus=256, frac_birth=0.0, frac_death=0.5):
+def query(model, sampler, unit, n_bins, n_chains, n_lineages, engine_mode, cus=256, frac_birth=0.0, frac_death=0.5, team=0,
+          chains_per_team=0):
     """lr_mcmc_query_layout on the host (no device needed), LR_DEVICE_CUS pinned: (rc, layout)."""
     from literate_amd import _hip
     lib = _hip.load()
-    cfg = make_config(model, sampler, unit, n_bins, n_chains, n_lineages, engine_mode, frac_birth, frac_death)
+    cfg = make_config(model, sampler, unit, n_bins, n_chains, n_lineages, engine_mode, frac_birth, frac_death, team,
+                      chains_per_team)
     lay = _hip.McmcLayout()
     old = os.environ.get("LR_DEVICE_CUS")
     os.environ["LR_DEVICE_CUS"] = str(cus)
@@ -260,21 +266,53 @@ def placed_lineages(n, rng):
     return extra
 
 
-def rj_reference(ts, te, model, n_bins, seed, n_it, chains=ORACLE_CHAINS):
-    """Binned statistics of the data (the oracle's own binning) and the oracle trajectories of `chains`."""
+def _grid(x, exact):
+    return np.round(x * 2.0 ** 32) / 2.0 ** 32 if exact else x
+
+
+@functools.lru_cache(maxsize=None)
+def lineages(n_bins, general, exact=True, n=3000):
+    """n synthetic lineages on [0, n_bins + 0.5] (unit resolution: integer births, deaths at .5) plus the placed ones; on
+    general times births and deaths move inside their bins (the pinned first birth and the extant lineages stay, so the
+    window stays n_bins), on the 2^-32 grid when `exact`."""
+    from literate_amd import synth
+    nb = int(n_bins)
+    ts, te, _ = synth.make_lineages(int(n), n_bins=nb, n_shifts=3, seed=nb + 1000 * general)
+    rng = np.random.default_rng(nb)
+    extra = [(float(s), k + 0.5) for s, k in placed_lineages(nb, rng)]
+    ts = np.concatenate([ts, [s for s, _ in extra]])
+    te = np.concatenate([te, [e for _, e in extra]])
+    if general:
+        keep_s, keep_e = ts == ts.min(), te >= te.max()
+        ts = np.where(keep_s, ts, ts + _grid(rng.uniform(0.0, 0.45, len(ts)), exact))
+        te = np.where(keep_e, te, te + _grid(rng.uniform(0.0, 0.45, len(te)), exact))
+    assert ts.min() == 0.0 and te.max() == nb + 0.5 and np.all(te > ts)
+    return ts, te
+
+
+def rj_stats(ts, te, model, n_bins):
+    """Binned statistics of the data (the oracle's own binning)."""
     from oracle import literate_oracle as lo
-    from oracle import mcmc_oracle as mo
     t0, sp, ex, br = lo.bin_events_cli(ts, te)
     assert t0 == 0 and len(sp) == n_bins
     stats = dict(sp=sp, ex=ex, br=br)
     if model == 3:
         stats["ex_dead"], stats["br_dead"] = lo.bin_events_dead(ts, te, te.max())
-    refs = {}
-    for c in chains:
-        with np.errstate(all="ignore"):
-            refs[c] = mo.run_mcmc(stats, ts.min(), te.max(), mo.Settings(model_BDI=model), mo.PhiloxDraws(seed, c), n_it, 1,
-                                  k_max=32)["mcmc"]
-    return stats, refs
+    return stats
+
+
+def rj_trajectory(stats, ts, te, model, seed, n_it, chain):
+    """The oracle's sampled rows of one chain, by its GLOBAL id (the draws are keyed by it)."""
+    from oracle import mcmc_oracle as mo
+    with np.errstate(all="ignore"):
+        return mo.run_mcmc(stats, ts.min(), te.max(), mo.Settings(model_BDI=model), mo.PhiloxDraws(seed, chain), n_it, 1,
+                           k_max=32)["mcmc"]
+
+
+def rj_reference(ts, te, model, n_bins, seed, n_it, chains=ORACLE_CHAINS):
+    """Binned statistics of the data (the oracle's own binning) and the oracle trajectories of `chains`."""
+    stats = rj_stats(ts, te, model, n_bins)
+    return stats, {c: rj_trajectory(stats, ts, te, model, seed, n_it, c) for c in chains}
 
 
 def check_forced(engine, cell):
@@ -294,33 +332,52 @@ def reference_loglik(ts, te, lam, mu, model, stats, pre):
     return lo.per_lineage_loglik(ts, te, 0.0, lam, mu, model, stats["br"], pre=pre)
 
 
-def run_rj_against_the_oracle(eng, ts, te, model, n_bins, stats, refs, n_it, cell):
-    """n_it iterations of an RJ engine (s_freq 1) in two launches: the chains of refs (rj_reference) row by row against
-    oracle/mcmc_oracle.run_mcmc (iteration and K columns exact, the head at rtol = atol = 1e-9), and every chain's
-    accepted state re-scored in fp64 by the oracle on the raw times and by lr_bd_loglik_batch (rtol 1e-9)."""
-    from literate_amd import ops
+def check_rj_rows(tr, refs, n_it, cell):
+    """Trace rows [samples, chains, LR_TRACE_W] against the oracle rows refs = {chain's index in tr: rows}: iteration
+    and K columns exact, the head at rtol = atol = 1e-9."""
     from literate_amd.engine import split_trace_row
-    from oracle import literate_oracle as lo
-    C = eng.n_chains
-    eng.init()
-    eng.steps(n_it // 2)
-    eng.steps(n_it - n_it // 2)
-    tr = eng.trace_rows()
     for c, ref in refs.items():
         for i in range(n_it):
             head, _, _ = split_trace_row(tr[i, c])
             r = ref[i]
             assert head[0] == r[0] and head[6] == r[6] and head[7] == r[7], (cell, c, i, head[:8], r[:8])
             assert np.allclose(head[:13], r[:13], rtol=1e-9, atol=1e-9), (cell, c, i, head, r)
-    snap = eng.snapshot()
+
+
+def check_rj_states(snap, ts, te, model, n_bins, stats, n_it, cell, pre=None):
+    """Every chain of a snapshot: n_it iterations done, a finite log-likelihood, and that log-likelihood equal to the fp64
+    oracle's for the chain's accepted state on the raw times (rtol 1e-9).  Returns the states' per-bin rates."""
+    from oracle import literate_oracle as lo
+    C = len(snap["likA"])
     assert np.all(snap["it"] == n_it) and np.all(np.isfinite(snap["likA"]))
     lam, mu = accepted_rates(snap, n_bins, C)
-    pre = lo.lineage_bins(ts, te, 0.0, n_bins)
+    if pre is None:
+        pre = lo.lineage_bins(ts, te, 0.0, n_bins)
     ref = np.array([reference_loglik(ts, te, lam[c], mu[c], model, stats, pre) for c in range(C)])
     assert np.allclose(snap["likA"], ref, rtol=1e-9, atol=0.0), (cell, snap["likA"] - ref)
+    return lam, mu
+
+
+def rescore_rj_on_device(eng, snap, lam, mu, model, stats, cell):
+    """Every chain's accepted state (its per-bin rates lam, mu) re-scored by lr_bd_loglik_batch on the engine's lineages."""
+    from literate_amd import ops
     lik = ops.bd_loglik_batch(eng.ts, eng.te, eng.t0, lam, mu, model, br_length=stats["br"],
                               end_time=eng.end_time).cpu().numpy()
     assert np.allclose(lik, snap["likA"], rtol=1e-9, atol=0.0), (cell, lik - snap["likA"])
+
+
+def run_rj_against_the_oracle(eng, ts, te, model, n_bins, stats, refs, n_it, cell):
+    """n_it iterations of an RJ engine (s_freq 1) in two launches: the chains of refs ({the chain's index in the engine:
+    its oracle rows}, rj_reference / rj_trajectory) row by row against oracle/mcmc_oracle.run_mcmc (iteration and K
+    columns exact, the head at rtol = atol = 1e-9), and every chain's accepted state re-scored in fp64 by the oracle on
+    the raw times and by lr_bd_loglik_batch (rtol 1e-9)."""
+    eng.init()
+    eng.steps(n_it // 2)
+    eng.steps(n_it - n_it // 2)
+    check_rj_rows(eng.trace_rows(), refs, n_it, cell)
+    snap = eng.snapshot()
+    lam, mu = check_rj_states(snap, ts, te, model, n_bins, stats, n_it, cell)
+    rescore_rj_on_device(eng, snap, lam, mu, model, stats, cell)
     return snap
 
 
@@ -351,15 +408,16 @@ def param_stats(kind, ts, te, n_bins):
     return (o, p, nsp, nex, dt, t_range), trend
 
 
-def param_reference(kind, bins, trend, n_it, s, seed, off):
-    """The oracle loops of the parametric samplers (DDRate -mBirth 2 -mDeath 2, trend_rate) for ORACLE_CHAINS."""
+def param_reference(kind, bins, trend, n_it, s, seed, off, chains=ORACLE_CHAINS):
+    """The oracle loops of the parametric samplers (DDRate -mBirth 2 -mDeath 2, trend_rate) for `chains` (indices in an
+    engine created with chain_offset = off: the draws are keyed by off + index)."""
     from oracle import dd_mcmc_oracle as ddo
     from oracle import trend_mcmc_oracle as tro
     o, p, nsp, nex, dt, t_range = bins
     with np.errstate(all="ignore"):
         emp = (nsp / dt, nex / dt)
     refs = {}
-    for c in ORACLE_CHAINS:
+    for c in chains:
         if kind == "dd":
             refs[c] = ddo.run_dd_mcmc(nsp, nex, dt, t_range, o, p, 2, 2, ddo.PhiloxDraws(seed, off + c), n_it, s, emp=emp)
         else:
@@ -388,27 +446,38 @@ def param_rates(kind, snap, dt, trend, n_chains):
     return [x.cpu().numpy() for x in (b, d)]
 
 
-def run_param_against_the_oracle(eng, kind, ts, te, bins, trend, emp, refs, n_it, s, cell):
-    """n_it iterations of a parametric engine in two launches: the sampled log rows of ORACLE_CHAINS (scalars and per-bin
+def check_param_rows(got, ref, n_rows, cell, c):
+    """One chain's log rows against the oracle's: the iteration column exact, 1e-9 on the rest and 1e-7 on the last three
+    (adequacy) columns - the tolerances of test_ddrate_sampler_follows_oracle."""
+    assert len(got) == len(ref) == n_rows
+    for i, (g, r) in enumerate(zip(got, ref)):
+        assert g[0] == r[0]
+        assert np.allclose(g[1:-3], r[1:-3], rtol=1e-9, atol=1e-9, equal_nan=True), (cell, c, i, g[:14], r[:14])
+        assert np.allclose(g[-3:], r[-3:], rtol=1e-7, atol=1e-9, equal_nan=True)
+
+
+def rescore_param_on_device(eng, kind, snap, ts, te, bins, trend, cell):
+    """Every chain's accepted parameter vector re-scored by lr_bd_loglik_batch on the raw times."""
+    from literate_amd import ops
+    o, p, nsp, nex, dt, t_range = bins
+    b, d = param_rates(kind, snap, dt, trend, eng.n_chains)
+    lik = ops.bd_loglik_batch(ts, te, o, b, d, 2).cpu().numpy()
+    assert np.allclose(lik, snap["likA"], rtol=1e-9), (cell, lik - snap["likA"])
+
+
+def run_param_against_the_oracle(eng, kind, ts, te, bins, trend, emp, refs, n_it, s, cell, chains=ORACLE_CHAINS):
+    """n_it iterations of a parametric engine in two launches: the sampled log rows of `chains` (scalars and per-bin
     columns) against the oracle loops with the tolerances of test_ddrate_sampler_follows_oracle, and every chain's
     accepted parameter vector re-scored by lr_bd_loglik_batch."""
-    from literate_amd import ops
     o, p, nsp, nex, dt, t_range = bins
     assert np.array_equal(eng.n_spec, nsp) and np.array_equal(eng.n_exti, nex) and np.allclose(eng.DT, dt, rtol=1e-13)
     eng.init()
     eng.steps(n_it // 2)
     eng.steps(n_it - n_it // 2)
-    for c in ORACLE_CHAINS:
-        got = eng.log_rows(c, emp=emp)
-        ref = refs[c]
-        assert len(got) == len(ref) == n_it // s
-        for i, (g, r) in enumerate(zip(got, ref)):
-            assert g[0] == r[0]
-            assert np.allclose(g[1:-3], r[1:-3], rtol=1e-9, atol=1e-9, equal_nan=True), (cell, c, i, g[:14], r[:14])
-            assert np.allclose(g[-3:], r[-3:], rtol=1e-7, atol=1e-9, equal_nan=True)
+    tr = eng.trace_rows()
+    for c in chains:
+        check_param_rows(eng.log_rows_from(tr[:, c], emp=emp), refs[c], n_it // s, cell, c)
     snap = eng.snapshot()
     assert np.all(snap["it"] == n_it)
-    b, d = param_rates(kind, snap, dt, trend, eng.n_chains)
-    lik = ops.bd_loglik_batch(ts, te, o, b, d, 2).cpu().numpy()
-    assert np.allclose(lik, snap["likA"], rtol=1e-9), (cell, lik - snap["likA"])
+    rescore_param_on_device(eng, kind, snap, ts, te, bins, trend, cell)
     return snap

@@ -28,28 +28,7 @@ def _gpu():
         pytest.fail("GPU tests need an MI355X: no ROCm device visible")
 
 
-def _grid(x, exact):
-    return np.round(x * 2.0 ** 32) / 2.0 ** 32 if exact else x
-
-
-@functools.lru_cache(maxsize=None)
-def _lineages(n_bins, general, exact=True):
-    """Synthetic lineages on [0, n_bins + 0.5] (unit resolution: integer births, deaths at .5) plus the placed ones; on
-    general times births and deaths move inside their bins (the pinned first birth and the extant lineages stay, so the
-    window stays n_bins), on the 2^-32 grid when `exact`."""
-    from literate_amd import synth
-    n = int(n_bins)
-    ts, te, _ = synth.make_lineages(3000, n_bins=n, n_shifts=3, seed=n + 1000 * general)
-    rng = np.random.default_rng(n)
-    extra = [(float(s), k + 0.5) for s, k in E.placed_lineages(n, rng)]
-    ts = np.concatenate([ts, [s for s, _ in extra]])
-    te = np.concatenate([te, [e for _, e in extra]])
-    if general:
-        keep_s, keep_e = ts == ts.min(), te >= te.max()
-        ts = np.where(keep_s, ts, ts + _grid(rng.uniform(0.0, 0.45, len(ts)), exact))
-        te = np.where(keep_e, te, te + _grid(rng.uniform(0.0, 0.45, len(te)), exact))
-    assert ts.min() == 0.0 and te.max() == n + 0.5 and np.all(te > ts)
-    return ts, te
+_lineages = E.lineages                      # (the builder: shared with tests/helpers/chain_edges.py)
 
 
 @functools.lru_cache(maxsize=None)
