@@ -653,6 +653,12 @@ int lr_mcmc_p4_resident(const lr_engine* e, int32_t out[4] /* host */);
  * kernel, without resident groups and under the environment variable LR_P4_PIPE=0, read where LR_P4_RESIDENT is, which
  * runs the resident trips one by one on every wave. */
 int lr_mcmc_p4_pipe(const lr_engine* e, int32_t out[4] /* host */);
+/* measurement hook: the two scanner waves of that kernel that make a chain's state-independent draws one step ahead run a
+ * lean form of the duty - the logarithm of the acceptance uniform rides in a free lane of the step's packed logarithm, the
+ * multiplier draws are made only for iterations that can read them; the same results bit for bit.  *out = 1 when the lean
+ * form runs, 0 for every other kernel, without the one-block form and under the environment variable LR_P4_LEAN_DRAWS=0,
+ * read where LR_P4_RESIDENT is, which runs the full duty. */
+int lr_mcmc_p4_draws(const lr_engine* e, int32_t* out /* host */);
 int lr_mcmc_destroy(lr_engine* e);
 
 #ifdef __cplusplus

@@ -138,6 +138,7 @@ SIGNATURES = {
     "lr_mcmc_p4_config": (c_i32, [c_vp, C.POINTER(c_i32)]),
     "lr_mcmc_p4_resident": (c_i32, [c_vp, C.POINTER(c_i32)]),
     "lr_mcmc_p4_pipe": (c_i32, [c_vp, C.POINTER(c_i32)]),
+    "lr_mcmc_p4_draws": (c_i32, [c_vp, C.POINTER(c_i32)]),
     "lr_mcmc_status": (c_i32, [c_vp, C.POINTER(c_i32), c_vp]),
     "lr_mcmc_warnings": (c_i32, [c_vp, C.POINTER(c_i32), c_vp]),
     "lr_mcmc_destroy": (c_i32, [c_vp]),

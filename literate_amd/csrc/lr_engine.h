@@ -46,6 +46,7 @@ struct lr_engine {
     int p4_cfg;               // ... and its configuration word (LR_P4_CFG_*, lr_p4_cfg_choice), latched with p4_help
     bool p4_resident;         // ... and whether its scanning lanes keep decoded groups in registers (lr_p4_resident_choice), latched with p4_help
     bool p4_pipe;             // ... and whether a wave's full set of resident trips runs as one block (lr_p4_pipe_choice), latched with p4_help
+    bool p4_lean;             // ... and whether waves 4, 5 run the lean draw duty (lr_p4_lean_choice), latched with p4_help
     bool packed_scan;         // launch-based engine whose scan kernel reads the PACKED lineages (lr_packscan.hip) instead of ts / te:
                               // planned (plan.packed_scan), dropped by init / restore if the packing
                               // refuses the input (unsorted beyond LR_MAX_RUNS runs)
@@ -102,6 +103,14 @@ static inline bool lr_p4_resident_choice(const lr_engine* e) {
 static inline bool lr_p4_pipe_choice(const lr_engine* e) {
     const char* env = getenv("LR_P4_PIPE");
     return lr_p4_resident_choice(e) && !(env && atoi(env) == 0);
+}
+
+// ... and the draw duty of its waves 4, 5 is the lean one (lr_persist4_kernel's LEAN, lr_spec_draw_lean in lr_step.h);
+// LR_P4_LEAN_DRAWS = 0: lr_spec_draw_both, the kernel without LEAN (A/B runs, the bit-equality test).  Evaluated where
+// lr_p4_help_choice is.
+static inline bool lr_p4_lean_choice(const lr_engine* e) {
+    const char* env = getenv("LR_P4_LEAN_DRAWS");
+    return lr_p4_pipe_choice(e) && !(env && atoi(env) == 0);
 }
 
 // Which instantiation of the speculative kernel an engine runs (lr_spec.h): 0 = a team per pair; a team per chain: 1 = in

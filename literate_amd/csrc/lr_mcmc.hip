@@ -227,8 +227,8 @@ typedef __attribute__((address_space(3))) int lr_lds_i32;
 // parametric samplers' only (four-chain kernel: the launch picks the instantiation - a stepper function that carries one
 // step is a third smaller, and the kernel's instruction footprint is shared by two CUs' instruction cache)
 // HAND: the proposal's tables are built by a helper wave from the segments this wave hands over (`hand`, epoch `hand_epoch`)
-// CFG: the four-chain kernel's configuration word (LR_P4_CFG_*, lr_step.h)
-template <int PB, int ES, bool PRE = false, int SAMPLER = -1, bool HAND = false, int CFG = LR_P4_CFG_GENERIC>
+// CFG: the four-chain kernel's configuration word (LR_P4_CFG_*, lr_step.h); LEAN: the draws come from lr_spec_draw_lean
+template <int PB, int ES, bool PRE = false, int SAMPLER = -1, bool HAND = false, int CFG = LR_P4_CFG_GENERIC, bool LEAN = false>
 __device__ __forceinline__ void lr_persist_step_body(const __attribute__((address_space(3))) lr_step_args* a3, int c, int lane,
                                                      __attribute__((address_space(3))) lr_seg_scratch* scratch3,
                                                      lr_lds_f64* st_f64, lr_lds_i32* st_i32, double lik, lr_lds_f64* table3,
@@ -246,7 +246,7 @@ __device__ __forceinline__ void lr_persist_step_body(const __attribute__((addres
     else if (PRE) {
         lr_rj_draws pre;
         lr_draws_load(draws, pre, lane);
-        lr_chain_step_core<true, PB, HAND, CFG>(st, a, 0, c, lane, (lr_seg_scratch*)scratch3, lik, reinterpret_cast<double2*>((double*)table3),
+        lr_chain_step_core<true, PB, HAND, CFG, LEAN>(st, a, 0, c, lane, (lr_seg_scratch*)scratch3, lik, reinterpret_cast<double2*>((double*)table3),
                                            table_es, br_lds, br_lds + LR_H_WIDE, &pre, hand, hand_epoch);
     } else
         lr_chain_step_core<true, PB>(st, a, 0, c, lane, (lr_seg_scratch*)scratch3, lik, reinterpret_cast<double2*>((double*)table3),
@@ -302,7 +302,8 @@ __device__ __attribute__((noinline)) void lr_persist_step(const __attribute__((a
 //   TAG: not used - the kernel's NR, so that the kernels with resident scan groups call instantiations of their own: the
 //   function is specialised for what its callers pass alike (LDS addresses among it), and a second caller of the
 //   instantiation of a kernel without resident groups would take that away from it
-template <int PB, int ES, int NW, int SAMPLER, bool HELP, int CFG = LR_P4_CFG_GENERIC, int TAG = 0>
+//   LEAN: the draws made ahead are lr_spec_draw_lean's (lr_persist4_kernel's LEAN)
+template <int PB, int ES, int NW, int SAMPLER, bool HELP, int CFG = LR_P4_CFG_GENERIC, int TAG = 0, bool LEAN = false>
 __device__ __attribute__((noinline)) void lr_persist4_steppers(const __attribute__((address_space(3))) lr_step_args* a3, int c0,
                                                                int n_chains, int wave, int lane,
                                                                __attribute__((address_space(3))) lr_seg_scratch* scratch3,
@@ -323,7 +324,7 @@ __device__ __attribute__((noinline)) void lr_persist4_steppers(const __attribute
                 double lik = 0.0;
 #pragma unroll
                 for (int w2 = 2; w2 < (ES == 2 /* unit resolution: the block's sums in slot 2 */ ? 3 : NW); ++w2) lik += red[(ph * NW + w2) * 2 + wave];
-                lr_persist_step_body<PB, ES, ES == 2 /* unit resolution: draws made ahead */ && SAMPLER == 0, SAMPLER, HELP, CFG>(
+                lr_persist_step_body<PB, ES, ES == 2 /* unit resolution: draws made ahead */ && SAMPLER == 0, SAMPLER, HELP, CFG, LEAN>(
                     a3, c, lane, scratch3, st_f64 + (2 * ph + wave) * (LR_STATE_ROWS * LR_ROW),
                     st_i32 + (2 * ph + wave) * (LR_ISTATE_ROWS * LR_ROW), lik, tab + ph * tab_doubles + wave, br3,
                     draws + (2 * ph + wave), HELP ? hands + wave : nullptr, (int)((2 * iter + ph + 1) & 0x3fffffff));
@@ -532,8 +533,12 @@ __global__ __launch_bounds__(T, LR_PERSIST_MINWAVES) void lr_persist_kernel(
 #ifndef LR_P4_PIPE
 #define LR_P4_PIPE 1          /* 0: the one-block form is not built */
 #endif
+// LEAN (PIPE > 0 only): the draw duty of waves 4, 5 is lr_spec_draw_lean (lr_step.h) - no logarithm of the acceptance
+// uniform (the stepper's packed lr_log takes it along in its free lane), the multiplier draws only in iterations that can
+// read them, the scalars stored by the lanes that drew them.  The Philox addresses, every value a step reads and every
+// floating-point operation on it are those of LEAN = false.  The launch picks (lr_p4_lean_choice).
 template <int H, bool GENERAL, bool PARAM /* a parametric sampler's chain step (DDRate, trend_rate) instead of the RJ sampler's */,
-          bool HELP = false, int CFG = LR_P4_CFG_GENERIC, int NR = 0, int PIPE = 0>
+          bool HELP = false, int CFG = LR_P4_CFG_GENERIC, int NR = 0, int PIPE = 0, bool LEAN = false>
 __global__ __launch_bounds__(LR_P4_THREADS, LR_P4_THREADS / 256) void lr_persist4_kernel(const lr_step_args* __restrict__ ap /* in global memory: a by-value argument struct measured
                                                                        0.2 us per launch faster, but one instantiation then kept a copy of it in scratch
                                                                        memory and read its fields from there in every phase */,
@@ -543,6 +548,7 @@ __global__ __launch_bounds__(LR_P4_THREADS, LR_P4_THREADS / 256) void lr_persist
     static_assert(CFG == LR_P4_CFG_GENERIC || (HELP && H <= 264), "a configuration word comes with the helper waves");
     static_assert(NR == 0 || HELP, "resident groups come with the helper waves");
     static_assert(PIPE == 0 || (PIPE == 1 && NR > 0), "the one-block form is one of the resident trips");
+    static_assert(!LEAN || PIPE > 0, "the lean draw duty comes with the one-block form");
     const lr_step_args& a = *ap;
     LR_PSTAMP(0);      // entry (LR_DIAG: wall-clock stamps of a launch's stages, blocks < 64; scratch/diag_p4_launch.py)
     constexpr int NW = LR_P4_THREADS / LR_WAVE;          // 16 waves: 2 steppers + 14 scanners (HELP: 2 + 2 helpers + 12)
@@ -595,7 +601,8 @@ __global__ __launch_bounds__(LR_P4_THREADS, LR_P4_THREADS / 256) void lr_persist
         const unsigned long long it = ((unsigned long long)(unsigned int)I[LR_I_IT_HI] << 32 | (unsigned int)I[LR_I_IT_LO]) + 1ull;
         lr_draw_slot* slot = &draws[ch];
         // (HELP: one wave per chain, one Philox call for both parts)
-        if (HELP) lr_spec_draw_both<CFG>(a_lds, (int)(blockIdx.x * 4) + ch, lane, it, slot);
+        if (LEAN) lr_spec_draw_lean<CFG>(a_lds, (int)(blockIdx.x * 4) + ch, lane, it, slot, I);
+        else if (HELP) lr_spec_draw_both<CFG>(a_lds, (int)(blockIdx.x * 4) + ch, lane, it, slot);
         else lr_spec_draw_part(a_lds, (int)(blockIdx.x * 4) + ch, lane, it, slot, q >> 1);
     };
     // a helper wave's table duty of a phase whose steppers advance pair `ph`: once the stepper has handed them over, the
@@ -767,7 +774,7 @@ __global__ __launch_bounds__(LR_P4_THREADS, LR_P4_THREADS / 256) void lr_persist
             }
         }
     } else if (!scanner)
-        lr_persist4_steppers<(H <= 264 ? lr_bins_per_lane(H) : 0), ES, NW, PARAM ? 1 : 0, HELP, CFG, NR + 64 * PIPE>(
+        lr_persist4_steppers<(H <= 264 ? lr_bins_per_lane(H) : 0), ES, NW, PARAM ? 1 : 0, HELP, CFG, NR + 64 * PIPE, LEAN>(
             (const __attribute__((address_space(3))) lr_step_args*)&a_lds, c0, C, wave, lane,
             (__attribute__((address_space(3))) lr_seg_scratch*)&scratch[wave], (lr_lds_f64*)&st_f64[0][0], (lr_lds_i32*)&st_i32[0][0],
             (lr_lds_f64*)&red[0][0][0], (lr_lds_f64*)reinterpret_cast<double*>(tab[0]), 2 * LR_UNIT_PLANES * H,
@@ -983,6 +990,7 @@ extern "C" int lr_mcmc_create(const lr_mcmc_config* cfg, const double* ts, const
     e->p4_cfg = lr_p4_cfg_choice(e);
     e->p4_resident = lr_p4_resident_choice(e);
     e->p4_pipe = lr_p4_pipe_choice(e);
+    e->p4_lean = lr_p4_lean_choice(e);
     e->streaming = false;
     e->packed_scan = plan.packed_scan;
     e->fork = nullptr;
@@ -1342,6 +1350,12 @@ extern "C" int lr_mcmc_steps(lr_engine* e, int64_t n_iters, void* stream_) {
         if (general && param) hipLaunchKernelGGL((lr_persist4_kernel<HH, true, true>), g4, b4, 0, stream, ap, pk, e->n8, e->p4, (long long)n, p4_carry);   \
         else if (general) hipLaunchKernelGGL((lr_persist4_kernel<HH, true, false>), g4, b4, 0, stream, ap, pk, e->n8, e->p4, (long long)n, p4_carry);      \
         else if (param) hipLaunchKernelGGL((lr_persist4_kernel<HH, false, true>), g4, b4, 0, stream, ap, pk, e->n8, e->p4, (long long)n, p4_carry);        \
+        else if (LR_P4_NR > 0 && LR_P4_PIPE > 0 && e->p4_help && e->p4_resident && e->p4_pipe && e->p4_lean && e->p4_cfg == LR_P4_CFG_BDI)   /* (the lean draw duty: lr_p4_lean_choice) */ \
+            hipLaunchKernelGGL((lr_persist4_kernel<(HH <= 264 ? HH : 264), false, false, true, LR_P4_CFG_BDI, LR_P4_NR, LR_P4_PIPE, true>), g4, b4, 0, stream, ap, pk, e->n8, e->p4, (long long)n, p4_carry); \
+        else if (LR_P4_NR > 0 && LR_P4_PIPE > 0 && e->p4_help && e->p4_resident && e->p4_pipe && e->p4_lean && e->p4_cfg == LR_P4_CFG_KEIDING)                                   \
+            hipLaunchKernelGGL((lr_persist4_kernel<(HH <= 264 ? HH : 264), false, false, true, LR_P4_CFG_KEIDING, LR_P4_NR, LR_P4_PIPE, true>), g4, b4, 0, stream, ap, pk, e->n8, e->p4, (long long)n, p4_carry); \
+        else if (LR_P4_NR > 0 && LR_P4_PIPE > 0 && e->p4_help && e->p4_resident && e->p4_pipe && e->p4_lean)                                                                     \
+            hipLaunchKernelGGL((lr_persist4_kernel<(HH <= 264 ? HH : 264), false, false, true, LR_P4_CFG_GENERIC, LR_P4_NR, LR_P4_PIPE, true>), g4, b4, 0, stream, ap, pk, e->n8, e->p4, (long long)n, p4_carry); \
         else if (LR_P4_NR > 0 && LR_P4_PIPE > 0 && e->p4_help && e->p4_resident && e->p4_pipe && e->p4_cfg == LR_P4_CFG_BDI)   /* (resident trips as one block: lr_p4_pipe_choice) */ \
             hipLaunchKernelGGL((lr_persist4_kernel<(HH <= 264 ? HH : 264), false, false, true, LR_P4_CFG_BDI, LR_P4_NR, LR_P4_PIPE>), g4, b4, 0, stream, ap, pk, e->n8, e->p4, (long long)n, p4_carry); \
         else if (LR_P4_NR > 0 && LR_P4_PIPE > 0 && e->p4_help && e->p4_resident && e->p4_pipe && e->p4_cfg == LR_P4_CFG_KEIDING)                                  \
@@ -1487,6 +1501,14 @@ extern "C" int lr_mcmc_p4_pipe(const lr_engine* e, int32_t* out) {
         else out[1] += mine >= LR_P4_NR;
     }
     out[3] = h >= LR_P4_RES_HELP ? 2 : 0;
+    return LR_OK;
+}
+
+// the draw duty of the four-chain kernel's waves 4, 5 in use: out = 1 for the lean form (lr_spec_draw_lean), 0 for
+// lr_spec_draw_both (LR_P4_LEAN_DRAWS=0, without the one-block form) and for every other kernel
+extern "C" int lr_mcmc_p4_draws(const lr_engine* e, int32_t* out) {
+    if (!e || !out) return LR_ERR_NULL;
+    *out = (e->plan.family == 2 && e->p4_help && e->p4_resident && e->p4_pipe && e->p4_lean && LR_P4_NR > 0 && LR_P4_PIPE > 0) ? 1 : 0;
     return LR_OK;
 }
 

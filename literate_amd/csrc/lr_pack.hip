@@ -212,6 +212,7 @@ static void lr_set_shares(lr_engine* e) {
     e->p4_cfg = lr_p4_cfg_choice(e);
     e->p4_resident = lr_p4_resident_choice(e);
     e->p4_pipe = lr_p4_pipe_choice(e);
+    e->p4_lean = lr_p4_lean_choice(e);
     if (e->lay.persistent == 2 && e->p4_help) {
         // a helper wave is idle until its stepper's hand-over arrives (~1.2 us into a phase, a scan trip takes ~0.3 us):
         // it scores the first groups meanwhile (the 128 helper lanes stride over [0, 128 trips), the scanners over the rest).

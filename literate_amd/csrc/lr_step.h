@@ -630,6 +630,46 @@ __device__ __forceinline__ void lr_spec_draw_both(const lr_step_args& a, int c, 
     if (lane < 8) out->sc[lane] = so;
 }
 
+// The LEAN form of lr_spec_draw_both (lr_persist4_kernel's LEAN): the same Philox call at the same addresses and the same
+// beta variate, without the work no result needs.
+//   - no logarithm: sc[0] holds the acceptance uniform ITSELF; the stepper's packed lr_log over the proposal's rates has
+//     lane 63 free for it (lr_propose_rj's LEAN, lr_stage_segments' `extra`) - lr_log is lane-wise and pure, so the step
+//     gets the double this duty used to compute on lane LR_UD_LANE
+//   - x, exp(x), da and their stores only when the iteration can be a multiplier move that reads them
+//     (lr_wave_multiplier_pre): r_a below d_freq = 0.8 and, for the process r_a selects, r_b < .5 or ONE rate in the state
+//     the step proposes from.  That state is the accepted one or the pending proposal, whichever way the pending decision
+//     goes; `I` is the chain's scalar row of st_i32 (LR_I_KL, LR_I_PKL, LR_I_KM, LR_I_PKM), which stands still while the
+//     chain's pair is scanned.  A skipped iteration leaves the slot's x / m / da stale: the step loads and drops them.
+//   - lanes LR_UD_LANE + 0..3 store their own uniforms into sc[0..6]; only r_a, r_b and q_b are broadcast, for the branches
+template <int CFG = LR_P4_CFG_GENERIC>
+__device__ __forceinline__ void lr_spec_draw_lean(const lr_step_args& a, int c, int lane, unsigned long long it, lr_draw_slot* out,
+                                                  const int* I) {
+    const lr_mcmc_config& cfg = a.cfg;
+    const lr_stream rng{(uint32_t)cfg.seed, (uint32_t)(cfg.chain_offset + c)};
+    const int ul = lane - LR_UD_LANE;
+    const uint32_t purpose = (ul < 0) ? LR_P_MULT : ((ul == 0) ? LR_P_ACCEPT : (ul == 1 ? LR_P_MOVE : LR_P_RJ));
+    const lr_u2 u = lr_pair(rng, it, purpose, ul < 0 ? (uint32_t)lane : (ul == 3 ? 1u : 0u));
+    const double r_a = lr_bcast(u.a, LR_UD_LANE + 1), r_b = lr_bcast(u.b, LR_UD_LANE + 1), q_b = lr_bcast(u.b, LR_UD_LANE + 2);
+    // one rate, accepted or pending: bits LR_I_KL, LR_I_PKL (birth) and LR_I_KM, LR_I_PKM (death) of one ballot
+    const unsigned int one = (unsigned int)__ballot(I[lane] == 1);
+    const double b_freq = cfg.const_death_rate ? 0.7 : 0.4;          // (lr_propose_rj's)
+    const bool one_rate = (one & (r_a < b_freq ? (1u << LR_I_KL | 1u << LR_I_PKL) : (1u << LR_I_KM | 1u << LR_I_PKM))) != 0u;
+    if (r_a < 0.8 && (r_b < .5 || one_rate)) {
+        const double x = a.mult_l * (u.b - .5);                            // LRF:165-176
+        out->x[lane] = x, out->m[lane] = exp(x), out->da[lane] = u.a;      // (lanes 0..31 are read)
+    }
+    double beta = 0.0;
+    if (!(r_a < 0.8) && r_a < 0.999 && (CFG != LR_P4_CFG_GENERIC || cfg.const_rates == 0) && q_b > 0.5) {
+        double ga, gb;
+        lr_wave_gamma2(rng, it, LR_P_BETA_A, LR_SHAPE_BETA_RJ, LR_P_BETA_B, LR_SHAPE_BETA_RJ, lane, &ga, &gb);
+        beta = ga / (ga + gb);
+    }
+    // slots: u (acceptance uniform), r_a, r_b, q_a, q_b, q2_a, q2_b, beta
+    if (ul >= 0 && ul < 4) out->sc[max(2 * ul - 1, 0)] = u.a;
+    if (ul >= 1 && ul < 4) out->sc[2 * ul] = u.b;
+    if (lane == 7) out->sc[7] = beta;
+}
+
 // Propose iteration `it` from the state `s` (LRF:234-304): on return `s` IS the proposal (a Gibbs step changes the
 // hyper-parameters, every other move the rates / times of one process), `p` its bookkeeping, and its lookup tables
 // stand at `table`.  A pure function of (s, it, the chain's Philox stream, the data): the speculative engine calls it
@@ -657,7 +697,10 @@ struct lr_table_hand {
 // table builder at all.  base_col is then the base state's whole table, `col_doubles` entries CS doubles apart.
 // CFG (four-chain kernel with helper waves): its configuration word - a specialised one fixes the switches the moves read
 // (LR_P4_CFG_*: const_rates == 0, use_rate_HP != 0, poisson_HP == 0); the tables are the helper's then.
-template <bool LDS_CONSTS = false, int PB = 0, int CS = 2, bool PAIR_PLANES = true, bool HAND = false, int CFG = LR_P4_CFG_GENERIC>
+// LEAN (with `pre`, made by lr_spec_draw_lean): pre->log_u holds the acceptance uniform itself, and its logarithm rides
+// along in the packed log of the rates as it does when the step draws by itself.
+template <bool LDS_CONSTS = false, int PB = 0, int CS = 2, bool PAIR_PLANES = true, bool HAND = false, int CFG = LR_P4_CFG_GENERIC,
+          bool LEAN = false>
 __device__ __forceinline__ void lr_propose_rj(const lr_step_args& a, int c, int lane, lr_seg_scratch* scratch_p,
                                               uint64_t it, lr_rj_state& s, lr_rj_prop& p, double2* table,
                                               int table_es, const lr_rj_draws* pre = nullptr,
@@ -667,6 +710,7 @@ __device__ __forceinline__ void lr_propose_rj(const lr_step_args& a, int c, int 
     static_assert(CS == 2 || (PB > 0 && !PAIR_PLANES), "a column of its own: one-pass builder, no pair planes");
     static_assert(!HAND || PB > 0, "a helper wave runs the one-pass builder");
     static_assert(CFG == LR_P4_CFG_GENERIC || HAND, "a configuration word comes with the helper waves");
+    static_assert(!LEAN || HAND, "the lean draw duty is one of the helper-wave form");
     lr_seg_scratch& scratch = *scratch_p;
     const lr_mcmc_config& cfg = a.cfg;
     constexpr bool fixed = CFG != LR_P4_CFG_GENERIC;     // the default switches as constants
@@ -690,7 +734,7 @@ __device__ __forceinline__ void lr_propose_rj(const lr_step_args& a, int c, int 
         const uint32_t purpose = (ul < 0) ? LR_P_MULT : ((ul == 0) ? LR_P_ACCEPT : (ul == 1 ? LR_P_MOVE : LR_P_RJ));
         ud = lr_pair(rng, it, purpose, ul < 0 ? (uint32_t)lane : (ul == 3 ? 1u : 0u));
     }
-    const double u_next = pre ? 1.0 : lr_bcast(ud.a, LR_UD_LANE);
+    const double u_next = pre ? (LEAN ? pre->log_u : 1.0) : lr_bcast(ud.a, LR_UD_LANE);
     LR_SSTAMP(2);
 
     double pL = L, pM = M, ptL = tL, ptM = tM;
@@ -789,7 +833,7 @@ __device__ __forceinline__ void lr_propose_rj(const lr_step_args& a, int c, int 
     // segments of the proposal -> LDS scratch (+ log of every rate in one call)
     double logpL, logpM, log_u_next;
     lr_stage_segments(&scratch, pL, pM, peL, peM, PKL, PKM, lane, &logpL, &logpM, u_next, &log_u_next);
-    if (pre) log_u_next = pre->log_u;
+    if (pre && !LEAN) log_u_next = pre->log_u;
 
     // the ranks of the bins can be taken over from the state the proposal was made from while no edge moved (every
     // multiplier move and Gibbs step, most of the no-op times moves); then, if no rate changed either, so can its column
@@ -866,8 +910,8 @@ __device__ __forceinline__ void lr_propose_rj(const lr_step_args& a, int c, int 
 // caller knows the proposal to be neither a Gibbs step nor invalid, and sets LR_S_LIK_P once the scan's sums are in)
 // HAND (four-chain kernel with helper waves): the proposal's lookup tables, pair planes and model constant are another
 // wave's (lr_propose_rj's HAND) - the scalar LR_S_CONST_P of the state then belongs to that wave, see lr_chain_store_handed
-// CFG: the four-chain kernel's configuration word (LR_P4_CFG_*), for the proposal
-template <bool LDS_CONSTS = false, int PB = 0, bool HAND = false, int CFG = LR_P4_CFG_GENERIC>
+// CFG: the four-chain kernel's configuration word (LR_P4_CFG_*), for the proposal; LEAN: lr_propose_rj's
+template <bool LDS_CONSTS = false, int PB = 0, bool HAND = false, int CFG = LR_P4_CFG_GENERIC, bool LEAN = false>
 __device__ __forceinline__ void lr_chain_step_core(lr_chain_regs& st, const lr_step_args& a, int mode, int c, int lane,
                                                    lr_seg_scratch* scratch_p, double lik_sum, double2* table,
                                                    int table_es = 2, const double* br_lds = nullptr,
@@ -931,7 +975,7 @@ __device__ __forceinline__ void lr_chain_step_core(lr_chain_regs& st, const lr_s
 
     // ---- propose iteration `it` (LRF:234-304) ----
     lr_rj_prop p;
-    if (HAND) lr_propose_rj<LDS_CONSTS, (PB > 0 ? PB : 1), 2, true, HAND, CFG>(a, c, lane, scratch_p, it, s, p, table, table_es, pre, br_lds, logbr_lds, nullptr, 0, 0.0, hand, hand_epoch);
+    if (HAND) lr_propose_rj<LDS_CONSTS, (PB > 0 ? PB : 1), 2, true, HAND, CFG, LEAN>(a, c, lane, scratch_p, it, s, p, table, table_es, pre, br_lds, logbr_lds, nullptr, 0, 0.0, hand, hand_epoch);
     else lr_propose_rj<LDS_CONSTS, PB>(a, c, lane, scratch_p, it, s, p, table, table_es, pre, br_lds, logbr_lds);
 
     // ---- back into the state registers ----

@@ -286,6 +286,13 @@ class ChainEngine:
         _hip.check(self.lib.lr_mcmc_p4_pipe(self.handle, out), "lr_mcmc_p4_pipe")
         return tuple(int(v) for v in out)
 
+    def p4_draws(self):
+        """Draw duty of the four-chain kernel steps() runs: "lean" (no logarithm, multiplier draws only for iterations that
+        can read them) or "full" (every other kernel, without the one-block form, or LR_P4_LEAN_DRAWS=0 at init())."""
+        w = C.c_int32(0)
+        _hip.check(self.lib.lr_mcmc_p4_draws(self.handle, C.byref(w)), "lr_mcmc_p4_draws")
+        return "lean" if w.value else "full"
+
     def timed_steps(self, n):
         """steps(n) bracketed by HIP events on the launch stream; returns elapsed device ms (blocks)."""
         ms = C.c_float(0.0)
