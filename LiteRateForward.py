@@ -10,6 +10,7 @@ process and the CLI's Gamma(2,2) rates; SURVEY.md section 8c 'config-1 note'), -
 what plotRJforward.v3.py derives from the logs, computed on the GPU).
 With --chains 1 the log file names are exactly the reference's; with more, chain k >= 0 writes
 <name>_c<k>_{mcmc,sp_rates,ex_rates}.log next to the shared _div.log.
+--replicates PATTERN runs the sampler on many replicate data sets in one launch (literate_amd/replicates.py).
 """
 import argparse
 import os
@@ -109,6 +110,14 @@ def build_parser():
     p.add_argument('--init_shifts', type=int, default=0, help='initial number of rate shifts per process')
     p.add_argument('--block', type=int, default=0, help='iterations per device window: logs are written and flushed and '
                    'the state is printed once per window, while the next one runs (default: -p rounded up to ~50000)')
+    p.add_argument('--replicates', type=str, default="", metavar='PATTERN', help='run on many replicate data sets at once (one '
+                   'stochastic imputation of the death times each): a glob or a comma-separated list of data files, expanded '
+                   'and sorted here; -d stays empty, --chains is the total and a multiple of the number of files; every '
+                   'replicate gets the reference\'s logs under its own file\'s literate_mcmc_logs/, the pooled --rtt, --rtt_bf, '
+                   '--ess and --combine outputs and <NAME>_div_replicates.tsv go under the first file\'s; the files must share '
+                   'their window of time bins (at most 512)')
+    p.add_argument('--replicates_name', type=str, default="", metavar='NAME', help='stem of the pooled outputs of --replicates '
+                   '(default: replicates<number of files>)')
     return p
 
 
@@ -142,6 +151,11 @@ def parse_data(args):
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
+    if args.replicates:
+        from literate_amd import replicates
+        err = replicates.arg_error(args, int(os.environ.get("WORLD_SIZE", "1")))
+        if err:
+            raise SystemExit(err)
     if args.rtt >= 0 and args.pyrate_output:
         raise SystemExit("--rtt bins the AD / TBP times of the logs; -pyrate_output flips them, which the reference's plot "
                          "does not bin the same way: not supported together")
@@ -190,6 +204,8 @@ def main(argv=None):
         if err:
             raise SystemExit(err)
     print("\n\n             LiteRate - 20200206 (MI355X engine)\n")
+    if args.replicates:
+        return replicates.run(args, parse_data)
     import torch
     import torch.distributed as dist
     from literate_amd import dist as lrd

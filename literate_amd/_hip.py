@@ -1,5 +1,6 @@
 """ctypes binding of libliterate_hip.so (include/literate_hip.h, include/literate_hip_age.h, include/literate_hip_ade.h,
-include/literate_hip_adej.h, include/literate_hip_mlik.h, include/literate_hip_tmlik.h).  Fails loudly: no fallback."""
+include/literate_hip_adej.h, include/literate_hip_mlik.h, include/literate_hip_tmlik.h, include/literate_hip_rjbin.h).  Fails loudly:
+no fallback."""
 import ctypes as C
 import os
 
@@ -16,6 +17,7 @@ LR_ADE_MAX_BINS = 512      # lr_ade_classes, lr_ade_profile (include/literate_hi
 LR_ADEJ_MAX_BINS, LR_ADEJ_MOVES, LR_ADEJ_STATE_W, LR_ADEJ_ROW_W = 128, 5, 96, 73      # include/literate_hip_adej.h
 LR_MLIK_MAX_BINS, LR_MLIK_MAX_TEMPS, LR_MLIK_MOVES, LR_MLIK_STATE_W, LR_MLIK_ROW_W = 512, 128, 2, 16, 12      # include/literate_hip_mlik.h
 LR_TMLIK_MAX_BINS, LR_TMLIK_MAX_TEMPS, LR_TMLIK_MAX_MODELS, LR_TMLIK_MOVES, LR_TMLIK_STATE_W, LR_TMLIK_ROW_W = 512, 128, 64, 2, 16, 12      # include/literate_hip_tmlik.h
+LR_RJBIN_MAX_BINS, LR_RJBIN_STATE_W = 512, 448      # include/literate_hip_rjbin.h
 LR_WARN_KCAP = 2
 LR_STATE_ROWS, LR_ISTATE_ROWS = 9, 5
 LR_TRACE_HEAD = 13
@@ -59,8 +61,17 @@ class TmlikProblem(C.Structure):
                 ("seed", C.c_uint64), ("stream", c_vp)]
 
 
+class RjbinProblem(C.Structure):
+    """lr_rjbin_problem (include/literate_hip_rjbin.h): the descriptor both lr_rjbin_* entry points take; the stream rides in it"""
+    _fields_ = [("sp", c_vp), ("ex", c_vp), ("br", c_vp), ("ex_dead", c_vp), ("br_dead", c_vp), ("start_time", c_vp),
+                ("end_time", c_vp), ("state", c_vp), ("warn", c_vp),
+                ("n_bins", c_i32), ("R", c_i32), ("chains_per_rep", c_i32), ("model", c_i32), ("const_rates", c_i32),
+                ("const_death_rate", c_i32), ("use_rate_HP", c_i32), ("chain0", c_i64), ("poisson_HP", c_f64),
+                ("update_fraction", c_f64), ("seed", C.c_uint64), ("stream", c_vp)]
+
+
 # name -> (restype, argtypes); exactly the symbols include/literate_hip.h, literate_hip_age.h, literate_hip_ade.h and
-# literate_hip_adej.h, literate_hip_mlik.h, literate_hip_tmlik.h declare (+ the RNG debug hook)
+# literate_hip_adej.h, literate_hip_mlik.h, literate_hip_tmlik.h, literate_hip_rjbin.h declare (+ the RNG debug hook)
 SIGNATURES = {
     "lr_version": (c_i32, []),
     "lr_bin_events_workspace_bytes": (c_i64, [c_i64, c_i32]),
@@ -120,6 +131,8 @@ SIGNATURES = {
     "lr_mlik_estimate": (c_i32, [c_vp, c_i64, c_i32, c_i32, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "lr_tmlik_init": (c_i32, [C.POINTER(TmlikProblem)]),
     "lr_tmlik_steps": (c_i32, [C.POINTER(TmlikProblem), c_i64, c_i64, c_i32, c_vp, c_i64, c_i64]),
+    "lr_rjbin_init": (c_i32, [C.POINTER(RjbinProblem), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "lr_rjbin_steps": (c_i32, [C.POINTER(RjbinProblem), c_i64, c_i64, c_i32, c_vp, c_i64, c_i64]),
     "lr_ess_summary_workspace_bytes": (c_i64, [c_i32, c_i32, c_i32, c_vp, c_i32, c_f64, c_i32]),
     "lr_ess_summary": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_i32, c_f64, c_i32, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
     "lr_col_summary_workspace_bytes": (c_i64, [c_i32, c_i32, c_i32, c_vp, c_i32, c_f64, c_i32, c_i32]),
@@ -205,7 +218,7 @@ def launch(fn, device, *args):
 
 
 def launch_problem(fn, device, problem, *args):
-    """Call an entry point that takes a descriptor with the stream in it (lr_tmlik_*): `device`'s current torch stream is put
+    """Call an entry point that takes a descriptor with the stream in it (lr_tmlik_*, lr_rjbin_*): `device`'s current torch stream is put
     into problem.stream, `device` made current for the call."""
     import torch
     with torch.cuda.device(device):

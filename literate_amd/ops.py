@@ -1125,6 +1125,106 @@ def tmlik_run(data, grid, wins, n_iter, s_freq, seed):
     return rows, state
 
 
+RJBIN_ROWS = {"L": 0, "M": 1, "tL": 2, "tM": 3, "eL": 4, "eM": 5, "scalars": 6}
+RJBIN_SCALARS = {"likA": 0, "priorA": 1, "priorPoiA": 2, "Gamma_rate_l": 3, "Gamma_rate_m": 4, "Poi_lambda": 5, "K_l": 6, "K_m": 7,
+                 "accepted": 8}
+RjbinSettings = namedtuple("RjbinSettings", "model const_rates const_death_rate use_rate_HP poisson_HP update_fraction",
+                           defaults=(2, 0, 0, 1, 0.0, 0.75))
+
+
+class RjbinData:
+    """The per-replicate statistics the RJ sampler's likelihood is a function of: sp, ex, br [R, n_bins] (and ex_dead, br_dead
+    for model 3) with start_time, end_time [R], as float64 device tensors, and the warning word: what every lr_rjbin_* call
+    of one run shares.  Chain c belongs to replicate c // chains_per_rep."""
+
+    def __init__(self, sp, ex, br, start_time, end_time, chains_per_rep, ex_dead=None, br_dead=None, device=None):
+        torch = _torch()
+        self.sp = _dev(sp, torch.float64, device)
+        if self.sp.dim() == 1:
+            self.sp = self.sp.reshape(1, -1)
+        self.device = self.sp.device
+        two = lambda x: None if x is None else _dev(x, torch.float64, self.device).reshape(-1, self.sp.shape[-1])
+        self.ex, self.br, self.ex_dead, self.br_dead = two(ex), two(br), two(ex_dead), two(br_dead)
+        self.start_time = _dev(start_time, torch.float64, self.device).reshape(-1)
+        self.end_time = _dev(end_time, torch.float64, self.device).reshape(-1)
+        self.R, self.n_bins = int(self.sp.shape[0]), int(self.sp.shape[1])
+        if self.sp.dim() != 2 or any(t is not None and tuple(t.shape) != (self.R, self.n_bins)
+                                     for t in (self.ex, self.br, self.ex_dead, self.br_dead)) \
+                or self.start_time.numel() != self.R or self.end_time.numel() != self.R:
+            raise ValueError("shape mismatch: sp, ex, br[, ex_dead, br_dead] [R, n_bins]; start_time, end_time [R]")
+        self.chains_per_rep = int(chains_per_rep)
+        self.n_chains = self.R * self.chains_per_rep
+        # (read and written, bits OR-ed in: the caller's to clear, so not an output of the seam)
+        self.warn = torch.zeros(1, dtype=torch.int32, device=self.device)
+
+    def warnings(self):
+        """the warning word (LR_WARN_* bits; a device read-back)"""
+        return int(self.warn.item())
+
+
+def rjbin_problem(data, state, seed, settings=RjbinSettings(), chain0=0):
+    """The descriptor of a call (_hip.RjbinProblem; it refers to the tensors of data and state: keep them alive while it is
+    used)."""
+    st = settings
+    return _hip.RjbinProblem(_hip.ptr(data.sp), _hip.ptr(data.ex), _hip.ptr(data.br), _hip.ptr(data.ex_dead), _hip.ptr(data.br_dead),
+                             _hip.ptr(data.start_time), _hip.ptr(data.end_time), _hip.ptr(state), _hip.ptr(data.warn),
+                             data.n_bins, data.R, data.chains_per_rep, int(st.model), int(st.const_rates), int(st.const_death_rate),
+                             int(st.use_rate_HP), int(chain0), float(st.poisson_HP), float(st.update_fraction),
+                             int(seed) & 0xFFFFFFFFFFFFFFFF, None)
+
+
+def rjbin_init(data, seed, settings=RjbinSettings(), chain0=0, init=None, out=None):
+    """The initial state of every chain (lr_rjbin_init) -> state [C, LR_RJBIN_STATE_W] (rows: RJBIN_ROWS, scalars:
+    RJBIN_SCALARS).  init: (L, M [C, <= LR_KMAX], tL, tM [C, <= LR_KMAX + 1], K_l, K_m [C]) to start from, padded here to the
+    ABI's widths; None: the CLI's start."""
+    torch = _torch()
+    lib = _hip.load()
+    C = data.n_chains
+    (state,) = _ade_out(out, ((max(C, 0), _hip.LR_RJBIN_STATE_W),), (torch.float64,), data.device, "(state,)")
+    six = [None] * 6
+    if init is not None:
+        L, M, tL, tM, KL, KM = init
+
+        def pad(x, w):
+            x = _host_f64(x).reshape(C, -1)
+            if x.shape[1] > w:
+                raise ValueError("init: at most LR_KMAX = %d rates (and one more time) per chain" % _hip.LR_KMAX)
+            full = np.zeros((C, w))
+            full[:, :x.shape[1]] = x
+            return _dev(full, torch.float64, data.device)
+        _check_host_K(KL, _hip.LR_KMAX, "K_l"), _check_host_K(KM, _hip.LR_KMAX, "K_m")
+        six = [pad(L, _hip.LR_KMAX), pad(M, _hip.LR_KMAX), pad(tL, _hip.LR_KMAX + 1), pad(tM, _hip.LR_KMAX + 1),
+               _dev(KL, torch.int32, data.device).reshape(-1), _dev(KM, torch.int32, data.device).reshape(-1)]
+        if six[4].numel() != C or six[5].numel() != C:
+            raise ValueError("init: K_l, K_m [C]")
+    rc = _hip.launch_problem(lib.lr_rjbin_init, data.device, rjbin_problem(data, state, seed, settings, chain0),
+                             *[_hip.ptr(t) for t in six])
+    _hip.check(rc, "lr_rjbin_init")
+    return state
+
+
+def rjbin_steps(data, state, it0, n_iters, s_freq, seed, settings=RjbinSettings(), chain0=0, rows=None, slot0=0, out=None):
+    """Iterations it0 .. it0 + n_iters - 1 of every chain of `state` (updated in place; lr_rjbin_steps) -> rows [cap, C,
+    LR_TRACE_W], the engines' trace rows.  rows: an earlier call's buffer to go on writing into at slot `slot0`; otherwise a
+    fresh one of exactly the rows due."""
+    torch = _torch()
+    lib = _hip.load()
+    C = data.n_chains
+    if state.dtype != torch.float64 or tuple(state.shape) != (C, _hip.LR_RJBIN_STATE_W) or not state.is_contiguous() \
+            or state.device != data.device:
+        raise ValueError("state must be rjbin_init's [C, LR_RJBIN_STATE_W] float64 tensor on the data's device")
+    n = rows_due(it0, n_iters, s_freq) if int(s_freq) >= 1 and int(n_iters) >= 0 and int(it0) >= 0 else 0
+    if rows is None:
+        (rows,) = _ade_out(out, ((max(n, 0), C, _hip.LR_TRACE_W),), (torch.float64,), data.device, "(rows,)")
+    elif rows.dtype != torch.float64 or rows.dim() != 3 or not rows.is_contiguous() or rows.device != data.device \
+            or tuple(rows.shape[1:]) != (C, _hip.LR_TRACE_W):
+        raise ValueError("rows must be a [cap, C, LR_TRACE_W] float64 tensor on the data's device")
+    rc = _hip.launch_problem(lib.lr_rjbin_steps, data.device, rjbin_problem(data, state, seed, settings, chain0), int(it0),
+                             int(n_iters), int(s_freq), _hip.ptr(rows) if rows.numel() else None, int(rows.shape[0]), int(slot0))
+    _hip.check(rc, "lr_rjbin_steps")
+    return rows
+
+
 EssSummary = namedtuple("EssSummary", "mean ess act se_mean stop_lag pooled_mean pooled_ess rhat n")
 EssSummary.__doc__ = """lr_ess_summary's results.  mean, ess, act (in samples), se_mean float64 and stop_lag int32: [C, K] per chain and
 column; pooled_mean, pooled_ess, rhat: [K]; n: rows kept per chain.  ESS and ACT are NaN, SE 0 and the stop lag 0 where a
