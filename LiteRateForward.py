@@ -11,6 +11,7 @@ what plotRJforward.v3.py derives from the logs, computed on the GPU).
 With --chains 1 the log file names are exactly the reference's; with more, chain k >= 0 writes
 <name>_c<k>_{mcmc,sp_rates,ex_rates}.log next to the shared _div.log.
 --replicates PATTERN runs the sampler on many replicate data sets in one launch (literate_amd/replicates.py).
+--mc3 T runs T - 1 heated chains beside every cold one, which swap their temperatures (literate_amd/mc3.py).
 """
 import argparse
 import os
@@ -116,6 +117,15 @@ def build_parser():
                    'replicate gets the reference\'s logs under its own file\'s literate_mcmc_logs/, the pooled --rtt, --rtt_bf, '
                    '--ess and --combine outputs and <NAME>_div_replicates.tsv go under the first file\'s; the files must share '
                    'their window of time bins (at most 512)')
+    p.add_argument('--mc3', type=int, default=1, metavar='T', help='Metropolis coupling: beside every cold chain run T - 1 heated chains '
+                   'on likelihood^beta * prior, which cross between numbers of rate shifts more easily and hand their states '
+                   'down by swaps (1 = off, at most 8; more than 4 with at most 256 time bins); --chains stays the number of '
+                   'cold chains, the only ones logged; works on -d FILE and on --replicates, through the replicate sampler '
+                   '(unit time bins, at most 512; not with --ppc, --ppc_age, --ade, --ade_joint, --waic, --loo, --checkpoint, '
+                   '--init_shifts, several ranks); writes <stem>_MC3.tsv: the ladder, the swap rate of every pair and the '
+                   'round trips of every ladder')
+    p.add_argument('--mc3_dt', type=float, default=0.1, help='heating increment of --mc3: beta_j = 1 / (1 + mc3_dt * j)')
+    p.add_argument('--mc3_every', type=int, default=100, help='iterations between two swap rounds of --mc3 (0: never)')
     p.add_argument('--replicates_name', type=str, default="", metavar='NAME', help='stem of the pooled outputs of --replicates '
                    '(default: replicates<number of files>)')
     return p
@@ -151,7 +161,12 @@ def parse_data(args):
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
-    if args.replicates:
+    if args.mc3 != 1:
+        from literate_amd import mc3
+        err = mc3.arg_error(args, int(os.environ.get("WORLD_SIZE", "1")))
+        if err:
+            raise SystemExit(err)
+    elif args.replicates:
         from literate_amd import replicates
         err = replicates.arg_error(args, int(os.environ.get("WORLD_SIZE", "1")))
         if err:
@@ -204,6 +219,8 @@ def main(argv=None):
         if err:
             raise SystemExit(err)
     print("\n\n             LiteRate - 20200206 (MI355X engine)\n")
+    if args.mc3 != 1:
+        return mc3.run(args, parse_data)
     if args.replicates:
         return replicates.run(args, parse_data)
     import torch

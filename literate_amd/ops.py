@@ -1225,6 +1225,94 @@ def rjbin_steps(data, state, it0, n_iters, s_freq, seed, settings=RjbinSettings(
     return rows
 
 
+def rjmc3_problem(data, state, swaps, seed, betas, swap_every=0, settings=RjbinSettings(), chain0=0):
+    """The descriptor of a call on temperature ladders (_hip.Rjmc3Problem; it refers to the tensors of data, state and swaps
+    and holds the host array of the betas: keep them alive while it is used).  betas: host floats [T], betas[0] = 1."""
+    import ctypes
+    st = settings
+    b = [float(x) for x in np.asarray(betas, dtype=float).ravel()]
+    host = (ctypes.c_double * max(len(b), 1))(*b)
+    prob = _hip.Rjmc3Problem(_hip.ptr(data.sp), _hip.ptr(data.ex), _hip.ptr(data.br), _hip.ptr(data.ex_dead), _hip.ptr(data.br_dead),
+                             _hip.ptr(data.start_time), _hip.ptr(data.end_time), _hip.ptr(state), _hip.ptr(data.warn),
+                             data.n_bins, data.R, data.chains_per_rep, int(st.model), int(st.const_rates), int(st.const_death_rate),
+                             int(st.use_rate_HP), int(chain0), float(st.poisson_HP), float(st.update_fraction),
+                             int(seed) & 0xFFFFFFFFFFFFFFFF, ctypes.cast(host, ctypes.c_void_p), _hip.ptr(swaps), len(b),
+                             int(swap_every), None)
+    prob.betas_host = host
+    return prob
+
+
+def rjmc3_init(data, seed, betas, settings=RjbinSettings(), chain0=0, init=None, out=None):
+    """The initial state of every replica of every ladder (lr_rjmc3_init) -> (state [G T, LR_RJBIN_STATE_W], swaps [G, T - 1, 2]
+    int64, zero): G = data.n_chains ladders of T = len(betas) replicas, replica w of ladder g at row g T + w, its position
+    (scalar LR_RJMC3_S_POS) = w.  init: as rjbin_init's, per replica [G T, ...].  A ladder of more than 4 temperatures holds at
+    most LR_RJMC3_WIDE_MAX_BINS = 256 bins (LR_ERR_SIZE)."""
+    torch = _torch()
+    lib = _hip.load()
+    T = int(np.asarray(betas).size)
+    G, C = data.n_chains, data.n_chains * T
+    state, swaps = _ade_out(out, ((max(C, 0), _hip.LR_RJBIN_STATE_W), (max(G, 0), max(T - 1, 0), 2)), (torch.float64, torch.int64),
+                            data.device, "(state, swaps)")
+    six = [None] * 6
+    if init is not None:
+        L, M, tL, tM, KL, KM = init
+
+        def pad(x, w):
+            x = _host_f64(x).reshape(C, -1)
+            if x.shape[1] > w:
+                raise ValueError("init: at most LR_KMAX = %d rates (and one more time) per replica" % _hip.LR_KMAX)
+            full = np.zeros((C, w))
+            full[:, :x.shape[1]] = x
+            return _dev(full, torch.float64, data.device)
+        _check_host_K(KL, _hip.LR_KMAX, "K_l"), _check_host_K(KM, _hip.LR_KMAX, "K_m")
+        six = [pad(L, _hip.LR_KMAX), pad(M, _hip.LR_KMAX), pad(tL, _hip.LR_KMAX + 1), pad(tM, _hip.LR_KMAX + 1),
+               _dev(KL, torch.int32, data.device).reshape(-1), _dev(KM, torch.int32, data.device).reshape(-1)]
+        if six[4].numel() != C or six[5].numel() != C:
+            raise ValueError("init: K_l, K_m [G T]")
+    prob = rjmc3_problem(data, state, swaps if swaps.numel() else None, seed, betas, 0, settings, chain0)
+    rc = _hip.launch_problem(lib.lr_rjmc3_init, data.device, prob, *[_hip.ptr(t) for t in six])
+    _hip.check(rc, "lr_rjmc3_init")
+    return state, swaps
+
+
+def rjmc3_steps(data, state, swaps, it0, n_iters, s_freq, seed, betas, swap_every, settings=RjbinSettings(), chain0=0, rows=None,
+                ladder=None, slot0=0, with_ladder=True, out=None):
+    """Iterations it0 .. it0 + n_iters - 1 of every replica (state and swaps updated in place; lr_rjmc3_steps), a swap round
+    after every iteration with (it + 1) % swap_every == 0 (0: never) -> (rows [cap, G, LR_TRACE_W], the trace rows of the
+    replica at position 0, the cold chain; ladder [cap, G, T, 4]: per position the replica there, its likA, K_l, K_m - None
+    when with_ladder is False).  rows, ladder: an earlier call's buffers to go on writing into at slot `slot0`; otherwise fresh
+    ones of exactly the rows due."""
+    torch = _torch()
+    lib = _hip.load()
+    T = int(np.asarray(betas).size)
+    G, C = data.n_chains, data.n_chains * T
+    if state.dtype != torch.float64 or tuple(state.shape) != (C, _hip.LR_RJBIN_STATE_W) or not state.is_contiguous() \
+            or state.device != data.device:
+        raise ValueError("state must be rjmc3_init's [G T, LR_RJBIN_STATE_W] float64 tensor on the data's device")
+    if swaps.dtype != torch.int64 or tuple(swaps.shape) != (G, max(T - 1, 0), 2) or not swaps.is_contiguous() or swaps.device != data.device:
+        raise ValueError("swaps must be rjmc3_init's [G, T - 1, 2] int64 tensor on the data's device")
+    n = rows_due(it0, n_iters, s_freq) if int(s_freq) >= 1 and int(n_iters) >= 0 and int(it0) >= 0 else 0
+    if rows is None:
+        shapes, dts = [(max(n, 0), G, _hip.LR_TRACE_W)], [torch.float64]
+        if with_ladder and ladder is None:
+            shapes.append((max(n, 0), G, T, _hip.LR_RJMC3_LADDER_W)), dts.append(torch.float64)
+        got = _ade_out(out, tuple(shapes), tuple(dts), data.device, "(rows, ladder)")
+        rows = got[0]
+        ladder = got[1] if len(got) > 1 else ladder
+    elif rows.dtype != torch.float64 or rows.dim() != 3 or not rows.is_contiguous() or rows.device != data.device \
+            or tuple(rows.shape[1:]) != (G, _hip.LR_TRACE_W):
+        raise ValueError("rows must be a [cap, G, LR_TRACE_W] float64 tensor on the data's device")
+    if ladder is not None and (ladder.dtype != torch.float64 or not ladder.is_contiguous() or ladder.device != data.device
+                               or tuple(ladder.shape) != (int(rows.shape[0]), G, T, _hip.LR_RJMC3_LADDER_W)):
+        raise ValueError("ladder must be a [cap, G, T, 4] float64 tensor with the rows' cap on the data's device")
+    prob = rjmc3_problem(data, state, swaps if swaps.numel() else None, seed, betas, swap_every, settings, chain0)
+    rc = _hip.launch_problem(lib.lr_rjmc3_steps, data.device, prob, int(it0), int(n_iters), int(s_freq),
+                             _hip.ptr(rows) if rows.numel() else None, _hip.ptr(ladder) if ladder is not None and ladder.numel() else None,
+                             int(rows.shape[0]), int(slot0))
+    _hip.check(rc, "lr_rjmc3_steps")
+    return rows, ladder
+
+
 EssSummary = namedtuple("EssSummary", "mean ess act se_mean stop_lag pooled_mean pooled_ess rhat n")
 EssSummary.__doc__ = """lr_ess_summary's results.  mean, ess, act (in samples), se_mean float64 and stop_lag int32: [C, K] per chain and
 column; pooled_mean, pooled_ess, rhat: [K]; n: rows kept per chain.  ESS and ACT are NaN, SE 0 and the stop lag 0 where a

@@ -324,16 +324,18 @@ def write_div_replicates(path, sp, ex, br):
             f.write("%d\t" % int(row[0]) + "\t".join(str(float(v)) for v in row[1:]) + "\n")
 
 
-def run(args, parse=None):
+def run(args, parse=None, files=None, name=None, engine=None, finish=None):
     """LiteRateForward.py --replicates PATTERN: every chain of every replicate in one engine; the reference's logs per
     replicate under its own file's literate_mcmc_logs/, flushed per --block window; the pooled outputs (--rtt, --rtt_bf,
-    --ess, --combine, <NAME>_div_replicates.tsv) under the first file's, stem NAME."""
+    --ess, --combine, <NAME>_div_replicates.tsv) under the first file's, stem NAME.
+    A caller that has checked the arguments itself (literate_amd/mc3.py) names the files, may name the stem, builds the engine
+    - engine(reps, n_chains, **ReplicateEngine's keywords) - and is called as finish(engine, stem) before the engine closes."""
     world = int(os.environ.get("WORLD_SIZE", "1"))
-    err = arg_error(args, world)
+    err = arg_error(args, world) if files is None else None
     if err:
         raise SystemExit(err)
     try:
-        files = expand_pattern(args.replicates)
+        files = expand_pattern(args.replicates) if files is None else list(files)
         cpr = chains_per_replicate(args.chains, len(files))
     except ValueError as e:
         raise SystemExit(str(e))
@@ -346,9 +348,9 @@ def run(args, parse=None):
     except ValueError as e:
         raise SystemExit(str(e))
     model, R = args.model_BDI, len(files)
-    name = args.replicates_name or default_name(R)
+    name = name or args.replicates_name or default_name(R)
     n_samples = (args.n + args.s - 1) // args.s if args.n > 0 else 0
-    eng = ReplicateEngine(reps, args.chains, model=model, seed=rseed, const_rates=args.const_rates,
+    eng = (engine or ReplicateEngine)(reps, args.chains, model=model, seed=rseed, const_rates=args.const_rates,
                           const_death_rate=args.const_death_rate, use_rate_HP=args.use_rate_HP, poisson_HP=args.Poisson_prior,
                           update_fraction=args.update_fraction, s_freq=args.s, n_trace_slots=n_samples)
     print("%d replicates, %d chains each, %d time bins from %d on" % (R, cpr, reps.n_bins, reps.t0))
@@ -416,5 +418,7 @@ def run(args, parse=None):
             body = f.read()
         with open(stem + "_ESS.tsv", "w") as f:
             f.write(ESS_NOTE % (R, cpr) + body)
+    if finish is not None:
+        finish(eng, stem)
     eng.close()
     torch.cuda.synchronize()
