@@ -451,6 +451,8 @@ typedef struct lr_mcmc_config {
     double t0;                /* first bin edge = int(min ts)                       */
     double start_time;        /* min(ts)  (LRF:473)                                 */
     double end_time;          /* max(te)  (LRF:474)                                 */
+    /* The Philox key of local chain c is ((uint32) seed, (uint32) (chain_offset + c)): both wrap modulo 2^32 (seed 2^32 + 5
+     * is seed 5, chain_offset 2^32 - 2 gives chain 2 the key 0; tests/test_hip_long_run.py). */
     uint64_t seed;
     int64_t chain_offset;     /* global index of local chain 0 (multi-GPU sharding) */
     /* unit-resolution data: 1 asserts that EVERY lineage has ts - floor(ts) == frac_birth and

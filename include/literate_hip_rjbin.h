@@ -78,6 +78,7 @@ typedef struct lr_rjbin_problem {
     double* state;             /* [C, LR_RJBIN_STATE_W] */
     uint32_t* warn;            /* one word; bits are OR-ed in, never cleared */
     int32_t n_bins, R, chains_per_rep, model, const_rates, const_death_rate, use_rate_HP;
+    /* The Philox key of chain c is ((uint32) seed, (uint32) (chain0 + c)): both wrap modulo 2^32 (tests/test_hip_long_run.py). */
     int64_t chain0;            /* Philox key of chain 0 */
     double poisson_HP;         /* 0: the Poisson rate is sampled, starting at 1 */
     double update_fraction;

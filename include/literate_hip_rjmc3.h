@@ -66,6 +66,8 @@ typedef struct lr_rjmc3_problem {
     double* state;             /* [G T, LR_RJBIN_STATE_W] */
     uint32_t* warn;            /* one word; bits are OR-ed in, never cleared */
     int32_t n_bins, R, chains_per_rep, model, const_rates, const_death_rate, use_rate_HP;
+    /* The Philox key of replica (g, w) is ((uint32) seed, (uint32) (chain0 + g T + w)), the swap uniforms' ((uint32) seed,
+     * (uint32) (chain0 + g T)): both wrap modulo 2^32, also inside a ladder (tests/test_hip_long_run.py). */
     int64_t chain0;            /* Philox key of replica 0 of ladder 0 */
     double poisson_HP;         /* 0: the Poisson rate is sampled, starting at 1 */
     double update_fraction;

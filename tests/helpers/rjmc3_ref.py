@@ -4,6 +4,7 @@
                      a state - with the one change that the likelihood difference of the acceptance test is times beta
     row_of           run_mcmc's row of a state
     swap_round       round n of a ladder: the pairs (j, j + 1), j = n % 2, n % 2 + 2, ...
+    run_chain_from   one chain at beta 1 from iteration it0 on (tests/helpers/long_run.py)
     run_ladder       T replicas, the swap rounds among their iterations, the rows of the replica at position 0, the ladder
                      buffer, the swap counts, the final states
 
@@ -142,21 +143,45 @@ def swap_round(n, pos, lik, betas, uniform, counts=None, margins=None):
     return pos
 
 
-def run_ladder(stats, start_time, end_time, st, seed, key0, betas, swap_every, n_it, s_freq, k_max=32, inits=None):
-    """One ladder: replica w draws from PhiloxDraws(seed, key0 + w) and starts at position w.  -> dict(mcmc, sp, ex: the rows of
-    the replica at position 0, as run_mcmc's; ladder [S, T, 4]; swaps [T - 1, 2]; states, pos: the final ones; margin: the
-    smallest of all decisions; overflows)"""
+def run_chain_from(stats, start_time, end_time, st, seed, key, it0, n_it, s_freq, k_max=32, remap=None):
+    """One chain (beta 1) from its initial state through iterations it0 .. it0 + n_it - 1, as lr_rjbin_steps runs them when it is
+    given it0: draws, rows (it % s_freq == 0) and the iteration column by the true iteration.  remap: iteration -> the address
+    the draws are made at instead (a broken counter, for the tests' power).  -> dict(mcmc, sp, ex: run_mcmc's rows; state: the
+    final one; margin: the smallest of the decisions; overflows)"""
+    at = remap or (lambda it: it)
+    draws = mo.PhiloxDraws(seed, key)
+    S = start(stats, start_time, end_time, st, draws)
+    out = dict(mcmc=[], sp=[], ex=[], overflows=0)
+    margins = []
+    for it in range(it0, it0 + n_it):
+        with np.errstate(all="ignore"):
+            out["overflows"] += step(S, stats, start_time, end_time, st, draws, at(it), 1.0, k_max, margins)
+        if it % s_freq == 0:
+            head, sp, ex = row_of(S, it, start_time, end_time)
+            out["mcmc"].append(head), out["sp"].append(sp), out["ex"].append(ex)
+    out["state"], out["margin"] = S, (min(margins) if margins else np.inf)
+    return out
+
+
+def run_ladder(stats, start_time, end_time, st, seed, key0, betas, swap_every, n_it, s_freq, k_max=32, inits=None, it0=0,
+               remap=None):
+    """One ladder: replica w draws from PhiloxDraws(seed, key0 + w) and starts at position w (the keys, the swap stream's key0
+    too, modulo 2^32); iterations it0 .. it0 + n_it - 1 from the initial states (lr_rjmc3_steps given it0: the swap rounds'
+    numbers and the rows follow the true iteration; remap: as run_chain_from's, the swap uniforms' address included).  ->
+    dict(mcmc, sp, ex: the rows of the replica at position 0, as run_mcmc's; ladder [S, T, 4]; swaps [T - 1, 2]; states, pos: the
+    final ones; margin: the smallest of all decisions; overflows)"""
     T = len(betas)
-    draws = [mo.PhiloxDraws(seed, key0 + w) for w in range(T)]
-    swap_stream = px.Stream(seed, key0)
+    at = remap or (lambda it: it)
+    draws = [mo.PhiloxDraws(seed, (key0 + w) % 2 ** 32) for w in range(T)]
+    swap_stream = px.Stream(seed, key0 % 2 ** 32)
     states = [start(stats, start_time, end_time, st, draws[w], None if inits is None else inits[w]) for w in range(T)]
     pos = list(range(T))
     out = dict(mcmc=[], sp=[], ex=[], ladder=[], swaps=[[0, 0] for _ in range(T - 1)], overflows=0)
     margins = []
-    for it in range(n_it):
+    for it in range(it0, it0 + n_it):
         for w in range(T):
             with np.errstate(all="ignore"):
-                out["overflows"] += step(states[w], stats, start_time, end_time, st, draws[w], it, betas[pos[w]], k_max, margins)
+                out["overflows"] += step(states[w], stats, start_time, end_time, st, draws[w], at(it), betas[pos[w]], k_max, margins)
         if it % s_freq == 0:
             head, sp, ex = row_of(states[pos.index(0)], it, start_time, end_time)
             out["mcmc"].append(head), out["sp"].append(sp), out["ex"].append(ex)
@@ -164,7 +189,7 @@ def run_ladder(stats, start_time, end_time, st, seed, key0, betas, swap_every, n
                                    float(len(states[pos.index(j)]["M"]))] for j in range(T)])
         if swap_every > 0 and (it + 1) % swap_every == 0:
             pos = swap_round((it + 1) // swap_every, pos, [s["likA"] for s in states], betas,
-                             lambda j: swap_stream.pair(it, P_SWAP, j)[0], out["swaps"], margins)
+                             lambda j: swap_stream.pair(at(it), P_SWAP, j)[0], out["swaps"], margins)
     out["ladder"], out["swaps"] = np.array(out["ladder"], dtype=float).reshape(-1, T, 4), np.array(out["swaps"], dtype=np.int64).reshape(T - 1, 2)
     out["states"], out["pos"], out["margin"] = states, pos, (min(margins) if margins else np.inf)
     return out
