@@ -92,11 +92,21 @@ def build_parser():
     p.add_argument('--loo_draws', type=int, default=1000, help='posterior draws PSIS-LOO is computed from (2 to 8192)')
     p.add_argument('--block', type=int, default=0, help='iterations per device window (logs are flushed once per window; '
                    'default: -p rounded up to ~50000)')
+    p.add_argument('--replicates', type=str, default='', help='run on many replicate data sets - stochastic imputations of the '
+                   'death times, say - in one launch: a comma-separated list of files and / or globs (quote them), each parsed '
+                   'and binned as -d would be; they must share their number of time bins (at most 512); -d stays empty and '
+                   '--chains, the total, is a multiple of the number of files; every replicate gets the reference\'s own log '
+                   'beside its own file, --ess and --summary pool all replicates beside the first (extension)')
+    p.add_argument('--replicates_name', type=str, default='', help='stem of the pooled outputs of --replicates (default: '
+                   'replicates<number of files>)')
     return p
 
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
+    if args.replicates:
+        from literate_amd import replicates_par
+        return replicates_par.run(args, 1)
     if args.ess != -1.0:
         from literate_amd.logs import ess_arg_error
         err = ess_arg_error(args.ess, args.n, args.s)

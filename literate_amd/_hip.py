@@ -1,5 +1,6 @@
 """ctypes binding of libliterate_hip.so (include/literate_hip.h, include/literate_hip_age.h, include/literate_hip_ade.h,
-include/literate_hip_adej.h, include/literate_hip_mlik.h, include/literate_hip_tmlik.h, include/literate_hip_rjbin.h, include/literate_hip_rjmc3.h).  Fails loudly:
+include/literate_hip_adej.h, include/literate_hip_mlik.h, include/literate_hip_tmlik.h, include/literate_hip_rjbin.h, include/literate_hip_rjmc3.h,
+include/literate_hip_parbin.h).  Fails loudly:
 no fallback."""
 import ctypes as C
 import os
@@ -20,6 +21,7 @@ LR_TMLIK_MAX_BINS, LR_TMLIK_MAX_TEMPS, LR_TMLIK_MAX_MODELS, LR_TMLIK_MOVES, LR_T
 LR_RJBIN_MAX_BINS, LR_RJBIN_STATE_W = 512, 448      # include/literate_hip_rjbin.h
 # include/literate_hip_rjmc3.h (LR_P_SWAP: csrc/lr_device.h, beside LR_P_INIT)
 LR_RJMC3_MAX_TEMPS, LR_RJMC3_S_POS, LR_RJMC3_LADDER_W, LR_RJMC3_WIDE_MAX_BINS, LR_P_SWAP = 8, 9, 4, 256, 11
+LR_PARBIN_MAX_BINS, LR_PARBIN_STATE_W = 512, 16      # include/literate_hip_parbin.h
 LR_WARN_KCAP = 2
 LR_STATE_ROWS, LR_ISTATE_ROWS = 9, 5
 LR_TRACE_HEAD = 13
@@ -77,8 +79,16 @@ class Rjmc3Problem(C.Structure):
     _fields_ = RjbinProblem._fields_[:-1] + [("betas", c_vp), ("swaps", c_vp), ("T", c_i32), ("swap_every", c_i32), ("stream", c_vp)]
 
 
+class ParbinProblem(C.Structure):
+    """lr_parbin_problem (include/literate_hip_parbin.h): the descriptor both lr_parbin_* entry points take; the stream rides in it"""
+    _fields_ = [("n_spec", c_vp), ("n_exti", c_vp), ("DT", c_vp), ("origin", c_vp), ("present", c_vp), ("trend", c_vp),
+                ("state", c_vp), ("n_bins", c_i32), ("R", c_i32), ("chains_per_rep", c_i32), ("sampler", c_i32),
+                ("m_birth", c_i32), ("m_death", c_i32), ("init_death", c_f64), ("chain0", c_i64), ("seed", C.c_uint64),
+                ("stream", c_vp)]
+
+
 # name -> (restype, argtypes); exactly the symbols include/literate_hip.h, literate_hip_age.h, literate_hip_ade.h and
-# literate_hip_adej.h, literate_hip_mlik.h, literate_hip_tmlik.h, literate_hip_rjbin.h, literate_hip_rjmc3.h declare (+ the RNG debug hook)
+# literate_hip_adej.h, literate_hip_mlik.h, literate_hip_tmlik.h, literate_hip_rjbin.h, literate_hip_rjmc3.h, literate_hip_parbin.h declare (+ the RNG debug hook)
 SIGNATURES = {
     "lr_version": (c_i32, []),
     "lr_bin_events_workspace_bytes": (c_i64, [c_i64, c_i32]),
@@ -142,6 +152,8 @@ SIGNATURES = {
     "lr_rjbin_steps": (c_i32, [C.POINTER(RjbinProblem), c_i64, c_i64, c_i32, c_vp, c_i64, c_i64]),
     "lr_rjmc3_init": (c_i32, [C.POINTER(Rjmc3Problem), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "lr_rjmc3_steps": (c_i32, [C.POINTER(Rjmc3Problem), c_i64, c_i64, c_i32, c_vp, c_vp, c_i64, c_i64]),
+    "lr_parbin_init": (c_i32, [C.POINTER(ParbinProblem)]),
+    "lr_parbin_steps": (c_i32, [C.POINTER(ParbinProblem), c_i64, c_i64, c_i32, c_vp, c_i64, c_i64]),
     "lr_ess_summary_workspace_bytes": (c_i64, [c_i32, c_i32, c_i32, c_vp, c_i32, c_f64, c_i32]),
     "lr_ess_summary": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_i32, c_f64, c_i32, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
     "lr_col_summary_workspace_bytes": (c_i64, [c_i32, c_i32, c_i32, c_vp, c_i32, c_f64, c_i32, c_i32]),
@@ -227,7 +239,7 @@ def launch(fn, device, *args):
 
 
 def launch_problem(fn, device, problem, *args):
-    """Call an entry point that takes a descriptor with the stream in it (lr_tmlik_*, lr_rjbin_*, lr_rjmc3_*): `device`'s current torch stream is put
+    """Call an entry point that takes a descriptor with the stream in it (lr_tmlik_*, lr_rjbin_*, lr_rjmc3_*, lr_parbin_*): `device`'s current torch stream is put
     into problem.stream, `device` made current for the call."""
     import torch
     with torch.cuda.device(device):

@@ -10,7 +10,9 @@
 // The DDRate likelihood is a function of the per-bin statistics alone (DD:71-107), so an iteration costs O(n_bins) whatever
 // the number of lineages: bin b sits in lane b % 64, at most 8 bins to a lane, and N_SPEC, N_EXTI and DT stay in registers for
 // the whole launch.  The eight parameters sit in lanes 0-7 and the proposal, prior and rate map are lr_dd.h's - the expressions
-// the DD engine evaluates.  No LDS, no barrier: a wave never waits for another.  Every sum is a fixed tree (lr_wave_sum over
+// the DD engine evaluates: lr_dd_update_freq(), lr_dd_prior() and lr_dd_bin_rates() are called from the chain's iteration,
+// which stands in lr_par_iter.h (lr_ddi_*) since lr_parbin.hip runs the same chain on replicate data sets.
+// No LDS, no barrier: a wave never waits for another.  Every sum is a fixed tree (lr_wave_sum over
 // the lanes, a lane's bins in order; the estimators: a thread's samples in order, the lanes, the four waves in order), no
 // floating-point atomics: a chain's bits depend on its own arguments alone.
 #include <climits>
@@ -21,6 +23,7 @@
 #include "../../include/literate_hip_mlik.h"
 #include "lr_dd.h"
 #include "lr_internal.h"
+#include "lr_par_iter.h"          // the chain and its iteration: shared with lr_parbin.hip
 
 #define LR_MLIK_THREADS 256
 #define LR_MLIK_WAVES (LR_MLIK_THREADS / LR_WAVE)
@@ -45,29 +48,6 @@ struct lr_mlik_temps {
     double beta[LR_MLIK_MAX_TEMPS], scale[LR_MLIK_MAX_TEMPS];
 };
 
-// a lane's bins: b = lane + 64 i, i < nb
-struct lr_mlik_bins {
-    double ns[LR_MLIK_BPL], ne[LR_MLIK_BPL], dt[LR_MLIK_BPL];
-    int nb;
-};
-
-// likelihood_function's sum (DD:101-107) under the parameters in lanes 0-7 of P; NaN -> -inf
-__device__ __forceinline__ double lr_mlik_loglik(double P, const lr_mlik_bins& B, const lr_mlik_cfg& cfg, int lane) {
-    const lr_dd_params p = lr_dd_unpack(P);
-    double acc = 0.0;
-#pragma unroll
-    for (int i = 0; i < LR_MLIK_BPL; ++i) {
-        const int b = lane + LR_WAVE * i;
-        if (i < B.nb && b < cfg.n_bins) {
-            double br, dr, niche, frac;
-            lr_dd_bin_rates(p, (double)b, B.dt[i], cfg.m_birth, cfg.m_death, &br, &dr, &niche, &frac);
-            acc += (lr_log(br) * B.ns[i] - br * B.dt[i]) + (lr_log(dr) * B.ne[i] - dr * B.dt[i]);
-        }
-    }
-    const double s = lr_wave_sum(acc);
-    return s != s ? -INFINITY : s;
-}
-
 __global__ __launch_bounds__(LR_MLIK_THREADS) void lr_mlik_chain_kernel(const double* __restrict__ n_spec,
                                                                          const double* __restrict__ n_exti,
                                                                          const double* __restrict__ DT, lr_mlik_cfg cfg,
@@ -80,81 +60,39 @@ __global__ __launch_bounds__(LR_MLIK_THREADS) void lr_mlik_chain_kernel(const do
     const int j = c % cfg.T;
     const double beta = tp.beta[j], scale = tp.scale[j];
     const lr_stream rng{cfg.seed, (uint32_t)(cfg.chain0 + c)};
-    lr_mlik_bins B;
-    B.nb = (cfg.n_bins + LR_WAVE - 1) / LR_WAVE;
-    double dt_max = -INFINITY;
-#pragma unroll
-    for (int i = 0; i < LR_MLIK_BPL; ++i) {
-        const int b = lane + LR_WAVE * i;
-        const bool in = i < B.nb && b < cfg.n_bins;
-        B.ns[i] = in ? n_spec[b] : 0.0, B.ne[i] = in ? n_exti[b] : 0.0, B.dt[i] = in ? DT[b] : 1.0;
-        if (in) dt_max = fmax(dt_max, B.dt[i]);
-    }
-    const double k0 = -lr_wave_min(-dt_max), log_k0 = lr_log(k0);        // PRIOR_K0_L = np.max(DT) (DD:45)
+    lr_par_bins<LR_MLIK_BPL, false> B;
+    const double dt_max = lr_par_load_bins<LR_MLIK_BPL, false>(B, n_spec, n_exti, DT, nullptr, cfg.n_bins, lane);
+    lr_ddi_run run;
+    run.origin = cfg.origin, run.present = cfg.present, run.beta = beta;
+    run.n_bins = cfg.n_bins, run.m_birth = cfg.m_birth, run.m_death = cfg.m_death;
+    lr_ddi_run_of(run, dt_max, scale, cfg.mult_l, lane);
     double* st = state + (size_t)c * LR_MLIK_STATE_W;
-    double A, likA, priorA, prop0, prop1, acc0, acc1;          // proposals made / accepted per move kind
+    lr_par_chain S;
     if (mode == 0) {
-        const double x0 = cfg.present - (cfg.origin + cfg.present) / 2.0;       // PRESENT - np.mean([ORIGIN, PRESENT])
-        const double init[LR_DD_NPAR] = {0.5, 1.5, x0, 10.0, 20000.0, cfg.init_death, 1.0, 1.0};
-        A = 0.0;
-#pragma unroll
-        for (int i = 0; i < LR_DD_NPAR; ++i) A = (lane == i) ? init[i] : A;
-        likA = lr_mlik_loglik(A, B, cfg, lane);
-        priorA = lr_dd_prior(A, cfg.origin, cfg.present, k0, log_k0, lane);
-        prop0 = prop1 = acc0 = acc1 = 0.0;
+        lr_ddi_start<LR_MLIK_BPL>(S, B, run, cfg.init_death, lane);
     } else {
-        A = lane < LR_DD_NPAR ? st[lane] : 0.0;
-        likA = st[LR_MLIK_S_LIK], priorA = st[LR_MLIK_S_PRIOR];
-        prop0 = st[LR_MLIK_S_PROPOSED], prop1 = st[LR_MLIK_S_PROPOSED + 1];
-        acc0 = st[LR_MLIK_S_ACCEPTED], acc1 = st[LR_MLIK_S_ACCEPTED + 1];
-        const bool niche = cfg.m_birth == 2 || cfg.m_death == 2;
-        const double f = lr_dd_update_freq(cfg.m_birth, cfg.m_death, lane);
-        const double mult_l = scale * cfg.mult_l, slide_d = 1.5 * scale, norm_d = 0.2 * scale;
+        S.A = lane < LR_DD_NPAR ? st[lane] : 0.0;
+        S.likA = st[LR_MLIK_S_LIK], S.priorA = st[LR_MLIK_S_PRIOR];
+        S.prop0 = st[LR_MLIK_S_PROPOSED], S.prop1 = st[LR_MLIK_S_PROPOSED + 1];
+        S.acc0 = st[LR_MLIK_S_ACCEPTED], S.acc1 = st[LR_MLIK_S_ACCEPTED + 1];
         const long long s = cfg.s_freq;
         long long slot = 0;
         for (long long it = it0; it < it0 + n_iters; ++it) {
-            // the wave-uniform draws in one Philox call: lane 0 the acceptance uniform, lane 1 the move selector, lane 2 the
-            // sliding-window uniform (as lr_propose_dd takes them)
-            const uint32_t purpose = lane == 0 ? LR_P_DD_ACCEPT : (lane == 1 ? LR_P_DD_MOVE : LR_P_DD_SLIDE);
-            const lr_u2 ud = lr_pair(rng, (uint64_t)it, purpose, 0u);
-            const double log_u = lr_bcast(lr_log(lane == 0 ? ud.a : 1.0), 0);
-            double P = A, hasting = 0.0;
-            int move;
-            if (lr_bcast(ud.b, 1) < 0.1 && niche) {
-                // update_sliding_win(x0, m = 0, M = PRESENT, d = 1.5 s) (lib:124-128)
-                double ii = lr_bcast(A, 2) + (lr_bcast(ud.a, 2) - .5) * slide_d;
-                if (ii > cfg.present) ii = cfg.present - (ii - cfg.present);
-                ii = fabs(ii);
-                if (lane == 2) P = ii;
-                if (cfg.m_death == -1) {
-                    const double z = lr_normal(rng, (uint64_t)it, LR_P_DD_SLIDE, 1);   // update_normal_nobound(k, d = 0.2 s) (lib:136-138)
-                    if (lane == 1) P = A + z * norm_d;
-                }
-                move = 1;
-            } else {
-                const lr_u2 d = lr_pair(rng, (uint64_t)it, LR_P_DD_MULT, lane);
-                hasting = lr_wave_multiplier(P, LR_DD_NPAR, d.a < f, d.b, mult_l, lane);   // lib:156-165
-                move = 0;
-            }
-            const double prior = lr_dd_prior(P, cfg.origin, cfg.present, k0, log_k0, lane);
-            const double lik = lr_mlik_loglik(P, B, cfg, lane);
-            const double dl = beta == 0.0 ? 0.0 : beta * (lik - likA);
-            const bool ok = (dl + (prior - priorA) + hasting > log_u) || it == 0;      // DD:211
-            prop0 += move ? 0.0 : 1.0, prop1 += move ? 1.0 : 0.0;
-            if (ok) A = P, likA = lik, priorA = prior, acc0 += move ? 0.0 : 1.0, acc1 += move ? 1.0 : 0.0;
+            lr_ddi_iterate<LR_MLIK_BPL>(S, B, run, rng, it, lane);          // lr_par_iter.h: shared with lr_parbin.hip
             if (it % s == 0) {
                 double* row = rows + ((size_t)slot * cfg.n_chains + c) * LR_MLIK_ROW_W;
                 slot += 1;
-                const double Aj = __shfl(A, (lane - 4) & (LR_WAVE - 1));        // rare path (sampling only)
+                const double Aj = __shfl(S.A, (lane - 4) & (LR_WAVE - 1));        // rare path (sampling only)
                 double h = Aj;
                 if (lane == 0) h = (double)it;
                 if (lane == 1) h = beta;
-                if (lane == 2) h = likA;
-                if (lane == 3) h = priorA;
+                if (lane == 2) h = S.likA;
+                if (lane == 3) h = S.priorA;
                 if (lane < LR_MLIK_ROW_W) row[lane] = h;
             }
         }
     }
+    const double A = S.A, likA = S.likA, priorA = S.priorA, prop0 = S.prop0, prop1 = S.prop1, acc0 = S.acc0, acc1 = S.acc1;
     double so = A;
     if (lane == LR_MLIK_S_LIK) so = likA;
     if (lane == LR_MLIK_S_PRIOR) so = priorA;

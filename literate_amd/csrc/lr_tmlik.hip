@@ -19,6 +19,7 @@
 #include "../../include/literate_hip_tmlik.h"
 #include "lr_dd.h"
 #include "lr_internal.h"
+#include "lr_par_iter.h"          // the chain and its iteration: shared with lr_parbin.hip
 
 #define LR_TMLIK_THREADS 256
 #define LR_TMLIK_WAVES (LR_TMLIK_THREADS / LR_WAVE)
@@ -51,30 +52,6 @@ struct lr_tmlik_tables {
 static_assert(sizeof(lr_tmlik_cfg) + sizeof(lr_tmlik_tables) + 7 * sizeof(void*) + 3 * sizeof(long long) < 4096,
               "the kernel arguments stay under 4 KB");
 
-// a lane's bins: b = lane + 64 i, i < nb; lt = lr_log of the chain's covariate
-struct lr_tmlik_bins {
-    double ns[LR_TMLIK_BPL], ne[LR_TMLIK_BPL], dt[LR_TMLIK_BPL], lt[LR_TMLIK_BPL];
-    int nb;
-};
-
-// likelihood_function's sum (trend_rate.py:89-91) under the parameters in lanes 0-5 of P; NaN -> -inf
-__device__ __forceinline__ double lr_tmlik_loglik(double P, const lr_tmlik_bins& B, int n_bins, int const_b, int const_d,
-                                                  int lane) {
-    const lr_trend_params p = lr_trend_unpack(P);
-    double acc = 0.0;
-#pragma unroll
-    for (int i = 0; i < LR_TMLIK_BPL; ++i) {
-        const int b = lane + LR_WAVE * i;
-        if (i < B.nb && b < n_bins) {
-            double br, dr;
-            lr_trend_bin_rates_log(p, B.lt[i], const_b, const_d, &br, &dr);
-            acc += (lr_log(br) * B.ns[i] - br * B.dt[i]) + (lr_log(dr) * B.ne[i] - dr * B.dt[i]);
-        }
-    }
-    const double s = lr_wave_sum(acc);
-    return s != s ? -INFINITY : s;
-}
-
 __global__ __launch_bounds__(LR_TMLIK_THREADS) void lr_tmlik_chain_kernel(
     const double* __restrict__ n_spec, const double* __restrict__ n_exti, const double* __restrict__ DT,
     const double* __restrict__ trends, const double* __restrict__ wins, lr_tmlik_cfg cfg, lr_tmlik_tables tb, int mode,
@@ -88,80 +65,44 @@ __global__ __launch_bounds__(LR_TMLIK_THREADS) void lr_tmlik_chain_kernel(
     const lr_stream rng{cfg.seed, (uint32_t)((tb.key0[m] + r) * cfg.T + j)};
     const double win = wins[(size_t)m * cfg.T + j];
     const double* trend = trends + (size_t)tb.col[m] * cfg.n_bins;
-    lr_tmlik_bins B;
-    B.nb = (cfg.n_bins + LR_WAVE - 1) / LR_WAVE;
-#pragma unroll
-    for (int i = 0; i < LR_TMLIK_BPL; ++i) {
-        const int b = lane + LR_WAVE * i;
-        const bool in = i < B.nb && b < cfg.n_bins;
-        B.ns[i] = in ? n_spec[b] : 0.0, B.ne[i] = in ? n_exti[b] : 0.0, B.dt[i] = in ? DT[b] : 1.0;
-        B.lt[i] = lr_log(in ? trend[b] : 1.0);
-    }
+    lr_par_bins<LR_TMLIK_BPL, true> B;          // (with lr_log of the chain's covariate)
+    lr_par_load_bins<LR_TMLIK_BPL, true>(B, n_spec, n_exti, DT, trend, cfg.n_bins, lane);
+    lr_tri_run run;
+    run.beta = beta, run.mult_l = scale * cfg.mult_l, run.win = win;
+    run.n_bins = cfg.n_bins, run.const_b = const_b, run.const_d = const_d;
+    lr_trend_update_freq(const_b, const_d, lane, &run.f_mult, &run.f_norm);
     double* st = state + (size_t)c * LR_TMLIK_STATE_W;
-    double A, likA, priorA, prop0, prop1, acc0, acc1;          // proposals made / accepted per move kind
+    lr_par_chain S;
     if (mode == 0) {
-        const double init[LR_TR_NPAR] = {.1, .1, 0.0, 0.0, 1.0, 1.0};          // trend_rate.py:137
-        A = 0.0;
-#pragma unroll
-        for (int i = 0; i < LR_TR_NPAR; ++i) A = (lane == i) ? init[i] : A;
-        likA = lr_tmlik_loglik(A, B, cfg.n_bins, const_b, const_d, lane);
-        priorA = lr_trend_prior(A, lane);
-        prop0 = prop1 = acc0 = acc1 = 0.0;
+        lr_tri_start<LR_TMLIK_BPL>(S, B, run, lane);
     } else {
-        A = lane < LR_TR_NPAR ? st[lane] : 0.0;
-        likA = st[LR_TMLIK_S_LIK], priorA = st[LR_TMLIK_S_PRIOR];
-        prop0 = st[LR_TMLIK_S_PROPOSED], prop1 = st[LR_TMLIK_S_PROPOSED + 1];
-        acc0 = st[LR_TMLIK_S_ACCEPTED], acc1 = st[LR_TMLIK_S_ACCEPTED + 1];
-        double f_mult, f_norm;
-        lr_trend_update_freq(const_b, const_d, lane, &f_mult, &f_norm);
-        const double mult_l = scale * cfg.mult_l;
+        S.A = lane < LR_TR_NPAR ? st[lane] : 0.0;
+        S.likA = st[LR_TMLIK_S_LIK], S.priorA = st[LR_TMLIK_S_PRIOR];
+        S.prop0 = st[LR_TMLIK_S_PROPOSED], S.prop1 = st[LR_TMLIK_S_PROPOSED + 1];
+        S.acc0 = st[LR_TMLIK_S_ACCEPTED], S.acc1 = st[LR_TMLIK_S_ACCEPTED + 1];
         // iterations to go until the next one with it % s_freq == 0: one 64-bit modulo per launch, not one per iteration
         long long until_row = (cfg.s_freq - it0 % cfg.s_freq) % cfg.s_freq;
         long long slot = cfg.slot0;
         for (long long it = it0; it < it0 + n_iters; ++it) {
-            // the wave-uniform draws in one Philox call: lane 0 the acceptance uniform, lane 1 the move selector (as the trend
-            // engine's proposal takes them)
-            const lr_u2 ud = lr_pair(rng, (uint64_t)it, lane == 0 ? LR_P_TR_ACCEPT : LR_P_TR_MOVE, 0u);
-            const double log_u = lr_bcast(lr_log(lane == 0 ? ud.a : 1.0), 0);
-            const lr_u2 d = lr_pair(rng, (uint64_t)it, LR_P_TR_MULT, lane);
-            double P = A, hasting = 0.0;
-            int move;
-            bool moved = true;
-            if (lr_bcast(ud.a, 1) < .33) {
-                const double z = lr_normal(rng, (uint64_t)it, LR_P_TR_NORM, lane);   // update_normal_nobound_vec (lib:140-146)
-                const bool fires = lane < LR_TR_NPAR && d.a < f_norm;
-                if (fires) P = A + z * win;
-                // a step whose mask fires for no slope proposes the state itself: it is always accepted and says nothing about
-                // the window, so it is not counted (the windows are tuned from these counters)
-                moved = __ballot(fires) != 0ull;
-                move = 1;
-            } else {
-                hasting = lr_wave_multiplier(P, LR_TR_NPAR, d.a < f_mult, d.b, mult_l, lane);   // lib:156-165
-                move = 0;
-            }
-            const double prior = lr_trend_prior(P, lane);
-            const double lik = lr_tmlik_loglik(P, B, cfg.n_bins, const_b, const_d, lane);
-            const double dl = beta == 0.0 ? 0.0 : beta * (lik - likA);
-            const bool ok = (dl + (prior - priorA) + hasting > log_u) || it == 0;      // trend_rate.py:176
-            prop0 += move ? 0.0 : 1.0, prop1 += (move && moved) ? 1.0 : 0.0;
-            if (ok) A = P, likA = lik, priorA = prior, acc0 += move ? 0.0 : 1.0, acc1 += (move && moved) ? 1.0 : 0.0;
+            lr_tri_iterate<LR_TMLIK_BPL>(S, B, run, rng, it, lane);          // lr_par_iter.h: shared with lr_parbin.hip
             const bool sample = until_row == 0;
             until_row = sample ? cfg.s_freq - 1 : until_row - 1;
             if (sample) {
                 double* row = rows + ((((size_t)m * cfg.rows_cap + slot) * cfg.R + r) * cfg.T + j) * LR_TMLIK_ROW_W;
                 slot += 1;
-                const double Aj = __shfl(A, (lane - 4) & (LR_WAVE - 1));        // rare path (sampling only)
+                const double Aj = __shfl(S.A, (lane - 4) & (LR_WAVE - 1));        // rare path (sampling only)
                 double h = Aj;
                 if (lane == 0) h = (double)it;
                 if (lane == 1) h = beta;
-                if (lane == 2) h = likA;
-                if (lane == 3) h = priorA;
+                if (lane == 2) h = S.likA;
+                if (lane == 3) h = S.priorA;
                 if (lane == 4 + LR_TR_NPAR) h = win;
                 if (lane == 5 + LR_TR_NPAR) h = (double)m;
                 if (lane < LR_TMLIK_ROW_W) row[lane] = h;
             }
         }
     }
+    const double A = S.A, likA = S.likA, priorA = S.priorA, prop0 = S.prop0, prop1 = S.prop1, acc0 = S.acc0, acc1 = S.acc1;
     double so = A;
     if (lane == LR_TMLIK_S_LIK) so = likA;
     if (lane == LR_TMLIK_S_PRIOR) so = priorA;

@@ -1225,6 +1225,81 @@ def rjbin_steps(data, state, it0, n_iters, s_freq, seed, settings=RjbinSettings(
     return rows
 
 
+PARBIN_STATE = {"args": 0, "lik": 8, "prior": 9, "proposed": 10, "accepted": 12}
+PARBIN_NPAR = {1: 8, 2: 6}
+# sampler 1: DDRate (m_birth, m_death as dd_rates; init_death = -fix_death); 2: trend_rate (m_birth, m_death = -const_B, -const_D)
+ParbinSettings = namedtuple("ParbinSettings", "sampler m_birth m_death init_death", defaults=(1, 2, 2, 0.1))
+
+
+class ParbinData:
+    """The per-replicate statistics the parametric samplers' likelihoods are functions of: n_spec, n_exti, DT [R, n_bins] with
+    origin, present [R] (create_bins' values) and, for trend_rate, the normalised covariate trend [n_bins] all replicates
+    share, as float64 device tensors: what every lr_parbin_* call of one run shares.  Chain c belongs to replicate c //
+    chains_per_rep."""
+
+    def __init__(self, n_spec, n_exti, DT, origin, present, chains_per_rep, trend=None, device=None):
+        torch = _torch()
+        self.n_spec = _dev(n_spec, torch.float64, device)
+        if self.n_spec.dim() == 1:
+            self.n_spec = self.n_spec.reshape(1, -1)
+        self.device = self.n_spec.device
+        two = lambda x: _dev(x, torch.float64, self.device).reshape(-1, self.n_spec.shape[-1])
+        self.n_exti, self.DT = two(n_exti), two(DT)
+        one = lambda x: _dev(x if isinstance(x, torch.Tensor) else np.atleast_1d(np.asarray(x, dtype=np.float64)), torch.float64,
+                             self.device).reshape(-1)
+        self.origin, self.present = one(origin), one(present)
+        self.trend = None if trend is None else _dev(trend, torch.float64, self.device).reshape(-1)
+        self.R, self.n_bins = int(self.n_spec.shape[0]), int(self.n_spec.shape[1])
+        if self.n_spec.dim() != 2 or any(tuple(t.shape) != (self.R, self.n_bins) for t in (self.n_exti, self.DT)) \
+                or self.origin.numel() != self.R or self.present.numel() != self.R \
+                or (self.trend is not None and self.trend.numel() != self.n_bins):
+            raise ValueError("shape mismatch: n_spec, n_exti, DT [R, n_bins]; origin, present [R]; trend [n_bins]")
+        self.chains_per_rep = int(chains_per_rep)
+        self.n_chains = self.R * self.chains_per_rep
+
+
+def parbin_problem(data, state, seed, settings=ParbinSettings(), chain0=0):
+    """The descriptor of a call (_hip.ParbinProblem; it refers to the tensors of data and state: keep them alive while it is
+    used)."""
+    st = settings
+    return _hip.ParbinProblem(_hip.ptr(data.n_spec), _hip.ptr(data.n_exti), _hip.ptr(data.DT), _hip.ptr(data.origin),
+                              _hip.ptr(data.present), _hip.ptr(data.trend), _hip.ptr(state), data.n_bins, data.R,
+                              data.chains_per_rep, int(st.sampler), int(st.m_birth), int(st.m_death), float(st.init_death),
+                              int(chain0), int(seed) & 0xFFFFFFFFFFFFFFFF, None)
+
+
+def parbin_init(data, seed, settings=ParbinSettings(), chain0=0, out=None):
+    """The initial state of every chain (lr_parbin_init) -> state [C, LR_PARBIN_STATE_W] (elements: PARBIN_STATE)."""
+    torch = _torch()
+    lib = _hip.load()
+    (state,) = _ade_out(out, ((max(data.n_chains, 0), _hip.LR_PARBIN_STATE_W),), (torch.float64,), data.device, "(state,)")
+    rc = _hip.launch_problem(lib.lr_parbin_init, data.device, parbin_problem(data, state, seed, settings, chain0))
+    _hip.check(rc, "lr_parbin_init")
+    return state
+
+
+def parbin_steps(data, state, it0, n_iters, s_freq, seed, settings=ParbinSettings(), chain0=0, rows=None, slot0=0, out=None):
+    """Iterations it0 .. it0 + n_iters - 1 of every chain of `state` (updated in place; lr_parbin_steps) -> rows [cap, C,
+    LR_TRACE_W], the engines' trace rows of the sampler.  rows: an earlier call's buffer to go on writing into at slot
+    `slot0`; otherwise a fresh one of exactly the rows due."""
+    torch = _torch()
+    lib = _hip.load()
+    C = data.n_chains
+    if state.dtype != torch.float64 or tuple(state.shape) != (C, _hip.LR_PARBIN_STATE_W) or not state.is_contiguous() \
+            or state.device != data.device:
+        raise ValueError("state must be parbin_init's [C, LR_PARBIN_STATE_W] float64 tensor on the data's device")
+    n = rows_due(it0, n_iters, s_freq) if int(s_freq) >= 1 and int(n_iters) >= 0 and int(it0) >= 0 else 0
+    if rows is None:
+        (rows,) = _ade_out(out, ((max(n, 0), C, _hip.LR_TRACE_W),), (torch.float64,), data.device, "(rows,)")
+    elif rows.dtype != torch.float64 or rows.dim() != 3 or not rows.is_contiguous() or rows.device != data.device \
+            or tuple(rows.shape[1:]) != (C, _hip.LR_TRACE_W):
+        raise ValueError("rows must be a [cap, C, LR_TRACE_W] float64 tensor on the data's device")
+    rc = _hip.launch_problem(lib.lr_parbin_steps, data.device, parbin_problem(data, state, seed, settings, chain0), int(it0),
+                             int(n_iters), int(s_freq), _hip.ptr(rows) if rows.numel() else None, int(rows.shape[0]), int(slot0))
+    _hip.check(rc, "lr_parbin_steps")
+    return rows
+
+
 def rjmc3_problem(data, state, swaps, seed, betas, swap_every=0, settings=RjbinSettings(), chain0=0):
     """The descriptor of a call on temperature ladders (_hip.Rjmc3Problem; it refers to the tensors of data, state and swaps
     and holds the host array of the betas: keep them alive while it is used).  betas: host floats [T], betas[0] = 1."""
