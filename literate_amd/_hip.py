@@ -1,6 +1,6 @@
 """ctypes binding of libliterate_hip.so (include/literate_hip.h, include/literate_hip_age.h, include/literate_hip_ade.h,
 include/literate_hip_adej.h, include/literate_hip_mlik.h, include/literate_hip_tmlik.h, include/literate_hip_rjbin.h, include/literate_hip_rjmc3.h,
-include/literate_hip_parbin.h).  Fails loudly:
+include/literate_hip_parbin.h, include/literate_hip_score.h).  Fails loudly:
 no fallback."""
 import ctypes as C
 import os
@@ -22,6 +22,7 @@ LR_RJBIN_MAX_BINS, LR_RJBIN_STATE_W = 512, 448      # include/literate_hip_rjbin
 # include/literate_hip_rjmc3.h (LR_P_SWAP: csrc/lr_device.h, beside LR_P_INIT)
 LR_RJMC3_MAX_TEMPS, LR_RJMC3_S_POS, LR_RJMC3_LADDER_W, LR_RJMC3_WIDE_MAX_BINS, LR_P_SWAP = 8, 9, 4, 256, 11
 LR_PARBIN_MAX_BINS, LR_PARBIN_STATE_W = 512, 16      # include/literate_hip_parbin.h
+LR_SCORE_MAX_SAMPLES, LR_SCORE_COLS = 4096, 6      # include/literate_hip_score.h
 LR_WARN_KCAP = 2
 LR_STATE_ROWS, LR_ISTATE_ROWS = 9, 5
 LR_TRACE_HEAD = 13
@@ -87,8 +88,15 @@ class ParbinProblem(C.Structure):
                 ("stream", c_vp)]
 
 
+class RttScoreProblem(C.Structure):
+    """lr_rtt_score_problem (include/literate_hip_score.h): the descriptor lr_rtt_score takes; the stream rides in it"""
+    _fields_ = [("trace", c_vp), ("truth", c_vp), ("rates", c_vp), ("shift_freq", c_vp), ("k_counts", c_vp), ("covered", c_vp),
+                ("score", c_vp), ("n_samples", c_i32), ("n_chains", c_i32), ("chains_per_group", c_i32), ("reserved", c_i32),
+                ("start_age", c_f64), ("end_age", c_f64), ("burnin", c_f64), ("stream", c_vp)]
+
+
 # name -> (restype, argtypes); exactly the symbols include/literate_hip.h, literate_hip_age.h, literate_hip_ade.h and
-# literate_hip_adej.h, literate_hip_mlik.h, literate_hip_tmlik.h, literate_hip_rjbin.h, literate_hip_rjmc3.h, literate_hip_parbin.h declare (+ the RNG debug hook)
+# literate_hip_adej.h, literate_hip_mlik.h, literate_hip_tmlik.h, literate_hip_rjbin.h, literate_hip_rjmc3.h, literate_hip_parbin.h, literate_hip_score.h declare (+ the RNG debug hook)
 SIGNATURES = {
     "lr_version": (c_i32, []),
     "lr_bin_events_workspace_bytes": (c_i64, [c_i64, c_i32]),
@@ -154,6 +162,7 @@ SIGNATURES = {
     "lr_rjmc3_steps": (c_i32, [C.POINTER(Rjmc3Problem), c_i64, c_i64, c_i32, c_vp, c_vp, c_i64, c_i64]),
     "lr_parbin_init": (c_i32, [C.POINTER(ParbinProblem)]),
     "lr_parbin_steps": (c_i32, [C.POINTER(ParbinProblem), c_i64, c_i64, c_i32, c_vp, c_i64, c_i64]),
+    "lr_rtt_score": (c_i32, [C.POINTER(RttScoreProblem)]),
     "lr_ess_summary_workspace_bytes": (c_i64, [c_i32, c_i32, c_i32, c_vp, c_i32, c_f64, c_i32]),
     "lr_ess_summary": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_i32, c_f64, c_i32, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
     "lr_col_summary_workspace_bytes": (c_i64, [c_i32, c_i32, c_i32, c_vp, c_i32, c_f64, c_i32, c_i32]),
@@ -239,7 +248,7 @@ def launch(fn, device, *args):
 
 
 def launch_problem(fn, device, problem, *args):
-    """Call an entry point that takes a descriptor with the stream in it (lr_tmlik_*, lr_rjbin_*, lr_rjmc3_*, lr_parbin_*): `device`'s current torch stream is put
+    """Call an entry point that takes a descriptor with the stream in it (lr_tmlik_*, lr_rjbin_*, lr_rjmc3_*, lr_parbin_*, lr_rtt_score): `device`'s current torch stream is put
     into problem.stream, `device` made current for the call."""
     import torch
     with torch.cuda.device(device):

@@ -664,6 +664,53 @@ def rtt_summary(trace, n_samples, start_age, end_age, burnin=0.2, pooled=True, w
     return RttSummary(time, rates, freq, kc, per * C if pooled else per)
 
 
+RttScore = namedtuple("RttScore", "time rates shift_freq k_counts covered score n_samples")
+RttScore.__doc__ = """lr_rtt_score's results (include/literate_hip_score.h).  time [n_bins] (host): rtt_time's bin centres; rates
+[G, 3, 3, n_bins], shift_freq [G, 2, n_bins], k_counts int64 [G, 2, LR_KMAX]: RttSummary's, one group per chains_per_group
+chains; covered int32 [G, 3, n_bins] and score [3, n_bins, 6] (groups, coverage, bias, mean absolute error, root mean squared
+error, mean HPD width), both None without a truth; n_samples: samples per group.  Device tensors."""
+
+
+def rtt_score(trace, n_samples, chains_per_group, start_age, end_age, truth=None, burnin=0.2):
+    """lr_rtt_summary(pooled) for every group of `chains_per_group` consecutive chains of trace rows [>= n_samples, C,
+    LR_TRACE_W] in one launch without a workspace (lr_rtt_score), bit for bit rtt_summary's values on the group's slice, and -
+    with truth [G, 2, n_bins] (birth, death; [2, n_bins]: the same for every group) - whether each group's 95 % HPD holds it
+    and the coverage, bias, errors and band width over the groups -> RttScore.  A group holds at most LR_SCORE_MAX_SAMPLES
+    samples after the burn-in."""
+    torch = _torch()
+    lib = _hip.load()
+    trace = _dev(trace, torch.float64)
+    if trace.dim() != 3 or trace.shape[2] != _hip.LR_TRACE_W or trace.shape[0] < int(n_samples):
+        raise ValueError("trace must be [>= n_samples, chains, LR_TRACE_W]")
+    S, C, cpg = int(n_samples), int(trace.shape[1]), int(chains_per_group)
+    if cpg < 1:
+        raise ValueError("chains_per_group must be at least 1, not %d" % cpg)
+    a, b = float(start_age), float(end_age)
+    time = rtt_time(a, b)
+    nb = time.size
+    G = C // cpg          # (chains that do not fill the groups: the library refuses, the outputs stay as they are)
+    dev = trace.device
+    rates = alloc_output((G, 3, 3, nb), torch.float64, dev)
+    freq = alloc_output((G, 2, nb), torch.float64, dev)
+    kc = alloc_output((G, 2, _hip.LR_KMAX), torch.int64, dev)
+    covered = score = None
+    if truth is not None:
+        truth = _dev(truth, torch.float64, dev)
+        if truth.dim() == 2:
+            truth = truth[None].expand(G, -1, -1).contiguous()
+        if tuple(truth.shape) != (G, 2, nb):
+            raise ValueError("truth must be [G, 2, n_bins] or [2, n_bins]: %d groups, %d bins" % (G, nb))
+        covered = alloc_output((G, 3, nb), torch.int32, dev)
+        score = alloc_output((3, nb, _hip.LR_SCORE_COLS), torch.float64, dev)
+    prob = _hip.RttScoreProblem(_hip.ptr(trace), _hip.ptr(truth), _hip.ptr(rates), _hip.ptr(freq), _hip.ptr(kc), _hip.ptr(covered),
+                                _hip.ptr(score), S, C, cpg, 0, a, b, float(burnin), None)
+    rc = _hip.launch_problem(lib.lr_rtt_score, dev, prob)
+    if rc == _hip.LR_ERR_SIZE and C % cpg:
+        raise ValueError("lr_rtt_score: LR_ERR_SIZE (%d chains are not a multiple of chains_per_group = %d)" % (C, cpg))
+    _hip.check(rc, "lr_rtt_score")
+    return RttScore(time, rates, freq, kc, covered, score, cpg * (S - int(burnin * S)))
+
+
 ShiftPrior = namedtuple("ShiftPrior", "totals shift_hist k_drawn k_accepted")
 ShiftPrior.__doc__ = """lr_shift_prior's counts (int64 device tensors).  totals [4]: accepted replicates, their shift times that fall
 in a bin, replicates the cap on K stopped, their shift times in all; shift_hist [n_bins]: the accepted shift times per unit

@@ -125,6 +125,28 @@ class Replicates:
         """data: [(ts, te)] per replicate, te with its jitter -> Replicates (binned through the same seam)"""
         return _assemble(paths or ["replicate%d" % r for r in range(len(data))], [(ts, te, 0.0) for ts, te in data], model)
 
+    @classmethod
+    def from_counts(cls, sp, ex, br, start_time, end_time, t0=0, paths=None):
+        """Per-bin statistics that somebody else has counted - a simulator's, say - as they are: sp, ex, br [R, n_bins] (or
+        [n_bins]: one replicate), start_time / end_time: one value for all replicates or [R] -> Replicates (model 0 - 2:
+        no ex_dead, br_dead)."""
+        sp, ex, br = [np.atleast_2d(np.asarray(x, dtype=np.float64)) for x in (sp, ex, br)]
+        if sp.ndim != 2 or sp.shape != ex.shape or sp.shape != br.shape or sp.shape[0] < 1:
+            raise ValueError("sp, ex and br must share their shape [R, n_bins]")
+        R, nb = sp.shape
+        if nb < 1 or nb > MAX_BINS:
+            raise ValueError("%d time bins; the replicate sampler holds 1 to %d" % (nb, MAX_BINS))
+        if not (np.all(np.isfinite(sp)) and np.all(np.isfinite(ex)) and np.all(np.isfinite(br))) or (sp < 0).any() or (ex < 0).any() \
+                or (br < 0).any():
+            raise ValueError("sp, ex and br must be finite and not negative")
+        start, end = [np.broadcast_to(np.asarray(x, dtype=np.float64), (R,)).copy() for x in (start_time, end_time)]
+        if not np.all(end > start):
+            raise ValueError("every end_time must lie after its start_time")
+        paths = list(paths) if paths is not None else ["replicate%d" % r for r in range(R)]
+        if len(paths) != R:
+            raise ValueError("paths names %d replicates, the statistics hold %d" % (len(paths), R))
+        return cls(paths, sp, ex, br, start, end, t0)
+
     def empirical(self, r):
         """(B_EMP, D_EMP) of replicate r, as the CLI computes them (LRF:566-568)"""
         with np.errstate(all="ignore"):
