@@ -1,6 +1,6 @@
 """ctypes binding of libliterate_hip.so (include/literate_hip.h, include/literate_hip_age.h, include/literate_hip_ade.h,
 include/literate_hip_adej.h, include/literate_hip_mlik.h, include/literate_hip_tmlik.h, include/literate_hip_rjbin.h, include/literate_hip_rjmc3.h,
-include/literate_hip_parbin.h, include/literate_hip_score.h).  Fails loudly:
+include/literate_hip_parbin.h, include/literate_hip_score.h, include/literate_hip_abc.h).  Fails loudly:
 no fallback."""
 import ctypes as C
 import os
@@ -23,6 +23,9 @@ LR_RJBIN_MAX_BINS, LR_RJBIN_STATE_W = 512, 448      # include/literate_hip_rjbin
 LR_RJMC3_MAX_TEMPS, LR_RJMC3_S_POS, LR_RJMC3_LADDER_W, LR_RJMC3_WIDE_MAX_BINS, LR_P_SWAP = 8, 9, 4, 256, 11
 LR_PARBIN_MAX_BINS, LR_PARBIN_STATE_W = 512, 16      # include/literate_hip_parbin.h
 LR_SCORE_MAX_SAMPLES, LR_SCORE_COLS = 4096, 6      # include/literate_hip_score.h
+# include/literate_hip_abc.h
+LR_ABC_NPAR, LR_ABC_MAX_LIVING, LR_ABC_SEARCH_CAP, LR_ABC_LDS_BINS, LR_P_ABC = 6, 1 << 24, 200, 1024, 56
+LR_ABC_FLAG_OVERFLOW, LR_ABC_FLAG_EXTINCT, LR_ABC_FLAG_REFUSED = 1, 2, 4
 LR_WARN_KCAP = 2
 LR_STATE_ROWS, LR_ISTATE_ROWS = 9, 5
 LR_TRACE_HEAD = 13
@@ -95,8 +98,21 @@ class RttScoreProblem(C.Structure):
                 ("start_age", c_f64), ("end_age", c_f64), ("burnin", c_f64), ("stream", c_vp)]
 
 
+class AbcProblem(C.Structure):
+    """lr_abc_problem (include/literate_hip_abc.h): the descriptor lr_abc_simulate takes; the stream rides in it"""
+    _fields_ = [("theta", c_vp), ("n_start", c_vp), ("sim_id", c_vp), ("obs", c_vp), ("weight", c_vp), ("dist", c_vp),
+                ("flags", c_vp), ("counts", c_vp), ("k_end", c_vp), ("n_sims", c_i64), ("id0", c_i64), ("n_bins", c_i32),
+                ("steps_per_bin", c_i32), ("max_living", c_i32), ("reserved", c_i32), ("seed", C.c_uint64), ("stream", c_vp)]
+
+
+class AbcBinomialProblem(C.Structure):
+    """lr_abc_binomial_problem (include/literate_hip_abc.h): the descriptor lr_abc_binomial takes; the stream rides in it"""
+    _fields_ = [("n", c_vp), ("p", c_vp), ("u", c_vp), ("x", c_vp), ("used", c_vp), ("N", c_i64), ("n_u", c_i32),
+                ("reserved", c_i32), ("stream", c_vp)]
+
+
 # name -> (restype, argtypes); exactly the symbols include/literate_hip.h, literate_hip_age.h, literate_hip_ade.h and
-# literate_hip_adej.h, literate_hip_mlik.h, literate_hip_tmlik.h, literate_hip_rjbin.h, literate_hip_rjmc3.h, literate_hip_parbin.h, literate_hip_score.h declare (+ the RNG debug hook)
+# literate_hip_adej.h, literate_hip_mlik.h, literate_hip_tmlik.h, literate_hip_rjbin.h, literate_hip_rjmc3.h, literate_hip_parbin.h, literate_hip_score.h, literate_hip_abc.h declare (+ the RNG debug hook)
 SIGNATURES = {
     "lr_version": (c_i32, []),
     "lr_bin_events_workspace_bytes": (c_i64, [c_i64, c_i32]),
@@ -163,6 +179,8 @@ SIGNATURES = {
     "lr_parbin_init": (c_i32, [C.POINTER(ParbinProblem)]),
     "lr_parbin_steps": (c_i32, [C.POINTER(ParbinProblem), c_i64, c_i64, c_i32, c_vp, c_i64, c_i64]),
     "lr_rtt_score": (c_i32, [C.POINTER(RttScoreProblem)]),
+    "lr_abc_simulate": (c_i32, [C.POINTER(AbcProblem)]),
+    "lr_abc_binomial": (c_i32, [C.POINTER(AbcBinomialProblem)]),
     "lr_ess_summary_workspace_bytes": (c_i64, [c_i32, c_i32, c_i32, c_vp, c_i32, c_f64, c_i32]),
     "lr_ess_summary": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_i32, c_f64, c_i32, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
     "lr_col_summary_workspace_bytes": (c_i64, [c_i32, c_i32, c_i32, c_vp, c_i32, c_f64, c_i32, c_i32]),
@@ -248,7 +266,7 @@ def launch(fn, device, *args):
 
 
 def launch_problem(fn, device, problem, *args):
-    """Call an entry point that takes a descriptor with the stream in it (lr_tmlik_*, lr_rjbin_*, lr_rjmc3_*, lr_parbin_*, lr_rtt_score): `device`'s current torch stream is put
+    """Call an entry point that takes a descriptor with the stream in it (lr_tmlik_*, lr_rjbin_*, lr_rjmc3_*, lr_parbin_*, lr_rtt_score, lr_abc_*): `device`'s current torch stream is put
     into problem.stream, `device` made current for the call."""
     import torch
     with torch.cuda.device(device):

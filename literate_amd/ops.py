@@ -711,6 +711,74 @@ def rtt_score(trace, n_samples, chains_per_group, start_age, end_age, truth=None
     return RttScore(time, rates, freq, kc, covered, score, cpg * (S - int(burnin * S)))
 
 
+AbcSims = namedtuple("AbcSims", "dist flags counts k_end")
+AbcSims.__doc__ = """lr_abc_simulate's results (include/literate_hip_abc.h).  dist [n_sims] (+inf where flagged); flags int32 [n_sims]
+(1 overflowed max_living, 2 extinct before the last step, 4 refused); counts int64 [n_sims, 4, n_bins] (births, deaths, living at
+the bin's start, lineage-steps) and k_end [n_sims], each None when not asked for.  Device tensors."""
+
+
+def abc_simulate(theta, n_start, obs, weight, steps_per_bin, max_living, seed, id0=0, sim_id=None, counts=False, k_end=False,
+                 device=None):
+    """Many simulations of the niche-construction model in one launch, one per lane, each with its distance to the observed
+    per-bin statistics (lr_abc_simulate) -> AbcSims.  theta [n_sims, 6]: l0, m0, K0, Kmax, g, h; n_start: an int or [n_sims];
+    obs, weight [3, n_bins]: birth rate, death rate, diversity at the start of the bin, and what each entry counts for (0: not
+    at all).  Simulation i has the id id0 + i, or sim_id[i]; what it computes depends on (seed, id, its theta and n_start, the
+    sizes, the tables) alone, so a second launch of chosen ids reproduces them."""
+    torch = _torch()
+    lib = _hip.load()
+    th = _dev(theta, torch.float64, device)
+    dev = th.device
+    if th.dim() == 1:
+        th = th[None, :]
+    if th.dim() != 2 or th.shape[1] != _hip.LR_ABC_NPAR:
+        raise ValueError("theta must be [n_sims, %d]" % _hip.LR_ABC_NPAR)
+    N = int(th.shape[0])
+    ob, w = _dev(obs, torch.float64, dev), _dev(weight, torch.float64, dev)
+    if ob.dim() != 2 or ob.shape[0] != 3 or w.shape != ob.shape:
+        raise ValueError("obs and weight must both be [3, n_bins]")
+    nb = int(ob.shape[1])
+    if isinstance(n_start, (int, np.integer)):
+        n0 = torch.full((N,), int(n_start), dtype=torch.int32, device=dev)
+    else:
+        n0 = _dev(n_start, torch.int32, dev).reshape(-1)
+        if n0.numel() != N:
+            raise ValueError("n_start must be an int or hold one entry per simulation")
+    ids = None
+    if sim_id is not None:
+        ids = _dev(sim_id, torch.int64, dev).reshape(-1)
+        if ids.numel() != N:
+            raise ValueError("sim_id must hold one entry per simulation")
+    dist = alloc_output(N, torch.float64, dev)
+    flags = alloc_output(N, torch.int32, dev)
+    cnt = alloc_output((N, 4, nb), torch.int64, dev) if counts else None
+    ke = alloc_output(N, torch.float64, dev) if k_end else None
+    prob = _hip.AbcProblem(_hip.ptr(th), _hip.ptr(n0), _hip.ptr(ids), _hip.ptr(ob), _hip.ptr(w), _hip.ptr(dist), _hip.ptr(flags),
+                           _hip.ptr(cnt), _hip.ptr(ke), N, int(id0), nb, int(steps_per_bin), int(max_living), 0,
+                           int(seed) & 0xFFFFFFFFFFFFFFFF, None)
+    _hip.check(_hip.launch_problem(lib.lr_abc_simulate, dev, prob), "lr_abc_simulate")
+    return AbcSims(dist, flags, cnt, ke)
+
+
+def abc_binomial(n, p, u, device=None):
+    """The simulator's binomial draw on given uniforms (lr_abc_binomial): n int32 [N], p [N], u [N, n_u] -> (x int32 [N], used
+    int32 [N]): the draws and the uniforms each consumed; x = -1 where the draw needs more than n_u uniforms (used: how many)
+    or its arguments are refused."""
+    torch = _torch()
+    lib = _hip.load()
+    n = _dev(n, torch.int32, device).reshape(-1)
+    dev = n.device
+    p = _dev(p, torch.float64, dev).reshape(-1)
+    u = _dev(u, torch.float64, dev)
+    N = int(n.numel())
+    if p.numel() != N or u.dim() != 2 or u.shape[0] != N:
+        raise ValueError("n and p must be [N], u [N, n_u]")
+    x = alloc_output(N, torch.int32, dev)
+    used = alloc_output(N, torch.int32, dev)
+    prob = _hip.AbcBinomialProblem(_hip.ptr(n), _hip.ptr(p), _hip.ptr(u), _hip.ptr(x), _hip.ptr(used), N, int(u.shape[1]), 0, None)
+    _hip.check(_hip.launch_problem(lib.lr_abc_binomial, dev, prob), "lr_abc_binomial")
+    return x, used
+
+
 ShiftPrior = namedtuple("ShiftPrior", "totals shift_hist k_drawn k_accepted")
 ShiftPrior.__doc__ = """lr_shift_prior's counts (int64 device tensors).  totals [4]: accepted replicates, their shift times that fall
 in a bin, replicates the cap on K stopped, their shift times in all; shift_hist [n_bins]: the accepted shift times per unit
