@@ -1,6 +1,6 @@
 """ctypes binding of libliterate_hip.so (include/literate_hip.h, include/literate_hip_age.h, include/literate_hip_ade.h,
 include/literate_hip_adej.h, include/literate_hip_mlik.h, include/literate_hip_tmlik.h, include/literate_hip_rjbin.h, include/literate_hip_rjmc3.h,
-include/literate_hip_parbin.h, include/literate_hip_score.h, include/literate_hip_abc.h).  Fails loudly:
+include/literate_hip_parbin.h, include/literate_hip_score.h, include/literate_hip_abc.h, include/literate_hip_trait.h).  Fails loudly:
 no fallback."""
 import ctypes as C
 import os
@@ -26,10 +26,15 @@ LR_SCORE_MAX_SAMPLES, LR_SCORE_COLS = 4096, 6      # include/literate_hip_score.
 # include/literate_hip_abc.h
 LR_ABC_NPAR, LR_ABC_MAX_LIVING, LR_ABC_SEARCH_CAP, LR_ABC_LDS_BINS, LR_P_ABC = 6, 1 << 24, 200, 1024, 56
 LR_ABC_FLAG_OVERFLOW, LR_ABC_FLAG_EXTINCT, LR_ABC_FLAG_REFUSED = 1, 2, 4
+# include/literate_hip_trait.h
+LR_TRAIT_F, LR_TRAIT_MAX_N, LR_TRAIT_CB, LR_TRAIT_TILE, LR_TRAIT_MAX_TILES = 38, 1 << 24, 8, 2048, 1024
+LR_P_TRAIT_MOVE, LR_P_TRAIT_ACCEPT = 60, 61
+LR_TRAIT_ROW_SCALARS, LR_TRAIT_ROW_WL, LR_TRAIT_ROW_WM, LR_TRAIT_STATE_W = 448, 512, 1024, 1536
 LR_WARN_KCAP = 2
 LR_STATE_ROWS, LR_ISTATE_ROWS = 9, 5
 LR_TRACE_HEAD = 13
 LR_TRACE_W = LR_TRACE_HEAD + 2 * (2 * LR_KMAX - 1)
+LR_TRAIT_ROW_W = LR_TRACE_W + 8
 LR_SIMBATCH_GROUPS, LR_SIMBATCH_LDS_SLOTS = 512, 16384      # lr_simulate_bd_batch: most workgroups, list positions in LDS
 LR_SHIFT_PRIOR_KCAP, LR_SHIFT_PRIOR_BLOCKS = 64, 768      # lr_shift_prior: most rates a replicate draws, most workgroups
 LR_ESS_LDS_ROWS = 16384      # lr_ess_summary: longest kept series held in LDS (longer ones stream from the workspace)
@@ -111,8 +116,25 @@ class AbcBinomialProblem(C.Structure):
                 ("reserved", c_i32), ("stream", c_vp)]
 
 
+class TraitWeightsProblem(C.Structure):
+    """lr_trait_weights_problem (include/literate_hip_trait.h): the descriptor lr_trait_weights takes; the stream rides in it"""
+    _fields_ = [("ts", c_vp), ("te", c_vp), ("x", c_vp), ("params", c_vp), ("W", c_vp), ("Slog_birth", c_vp), ("Slog_death", c_vp),
+                ("workspace", c_vp), ("workspace_bytes", c_i64), ("n", c_i64), ("t0", c_f64), ("n_bins", c_i32), ("C", c_i32),
+                ("stream", c_vp)]
+
+
+class TraitProblem(C.Structure):
+    """lr_trait_problem (include/literate_hip_trait.h): the descriptor both sampler entry points take; the stream rides in it"""
+    _fields_ = [("ts", c_vp), ("te", c_vp), ("x", c_vp), ("sp", c_vp), ("ex", c_vp), ("state", c_vp), ("warn", c_vp),
+                ("workspace", c_vp), ("workspace_bytes", c_i64), ("n", c_i64), ("chain0", c_i64), ("t0", c_f64),
+                ("start_time", c_f64), ("end_time", c_f64), ("poisson_HP", c_f64), ("update_fraction", c_f64),
+                ("win_x0", c_f64 * 2), ("win_kappa", c_f64 * 2), ("x0_lo", c_f64), ("x0_hi", c_f64),
+                ("n_bins", c_i32), ("C", c_i32), ("const_rates", c_i32), ("const_death_rate", c_i32), ("use_rate_HP", c_i32),
+                ("trait_every", c_i32), ("seed", C.c_uint64), ("stream", c_vp)]
+
+
 # name -> (restype, argtypes); exactly the symbols include/literate_hip.h, literate_hip_age.h, literate_hip_ade.h and
-# literate_hip_adej.h, literate_hip_mlik.h, literate_hip_tmlik.h, literate_hip_rjbin.h, literate_hip_rjmc3.h, literate_hip_parbin.h, literate_hip_score.h, literate_hip_abc.h declare (+ the RNG debug hook)
+# literate_hip_adej.h, literate_hip_mlik.h, literate_hip_tmlik.h, literate_hip_rjbin.h, literate_hip_rjmc3.h, literate_hip_parbin.h, literate_hip_score.h, literate_hip_abc.h, literate_hip_trait.h declare (+ the RNG debug hook)
 SIGNATURES = {
     "lr_version": (c_i32, []),
     "lr_bin_events_workspace_bytes": (c_i64, [c_i64, c_i32]),
@@ -181,6 +203,12 @@ SIGNATURES = {
     "lr_rtt_score": (c_i32, [C.POINTER(RttScoreProblem)]),
     "lr_abc_simulate": (c_i32, [C.POINTER(AbcProblem)]),
     "lr_abc_binomial": (c_i32, [C.POINTER(AbcBinomialProblem)]),
+    "lr_trait_weights_workspace_bytes": (c_i64, [c_i64, c_i32, c_i32]),
+    "lr_trait_weights_plan": (c_i32, [c_i64, c_i32, c_i32, C.POINTER(c_i32)]),
+    "lr_trait_weights": (c_i32, [C.POINTER(TraitWeightsProblem)]),
+    "lr_trait_workspace_bytes": (c_i64, [c_i64, c_i32, c_i32]),
+    "lr_trait_init": (c_i32, [C.POINTER(TraitProblem), c_vp]),
+    "lr_trait_steps": (c_i32, [C.POINTER(TraitProblem), c_i64, c_i64, c_i32, c_vp, c_i64, c_i64]),
     "lr_ess_summary_workspace_bytes": (c_i64, [c_i32, c_i32, c_i32, c_vp, c_i32, c_f64, c_i32]),
     "lr_ess_summary": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_i32, c_f64, c_i32, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
     "lr_col_summary_workspace_bytes": (c_i64, [c_i32, c_i32, c_i32, c_vp, c_i32, c_f64, c_i32, c_i32]),
@@ -266,7 +294,7 @@ def launch(fn, device, *args):
 
 
 def launch_problem(fn, device, problem, *args):
-    """Call an entry point that takes a descriptor with the stream in it (lr_tmlik_*, lr_rjbin_*, lr_rjmc3_*, lr_parbin_*, lr_rtt_score, lr_abc_*): `device`'s current torch stream is put
+    """Call an entry point that takes a descriptor with the stream in it (lr_tmlik_*, lr_rjbin_*, lr_rjmc3_*, lr_parbin_*, lr_rtt_score, lr_abc_*, lr_trait_*): `device`'s current torch stream is put
     into problem.stream, `device` made current for the call."""
     import torch
     with torch.cuda.device(device):

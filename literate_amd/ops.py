@@ -1509,6 +1509,192 @@ column; pooled_mean, pooled_ess, rhat: [K]; n: rows kept per chain.  ESS and ACT
 chain's column is constant after burn-in.  Device tensors."""
 
 
+def trait_weights_plan(n, n_bins, n_states):
+    """The launch shape lr_trait_weights uses (lr_trait_weights_plan) -> dict(cb, tiles, passes, copies)"""
+    import ctypes
+    lib = _hip.load()
+    out = (ctypes.c_int32 * 4)()
+    _hip.check(lib.lr_trait_weights_plan(int(n), int(n_bins), int(n_states), out), "lr_trait_weights_plan")
+    return dict(cb=out[0], tiles=out[1], passes=out[2], copies=out[3])
+
+
+def trait_weights(ts, te, x, t0, n_bins, params, out=None):
+    """The trait-weighted exposures of C states (lr_trait_weights, include/literate_hip_trait.h): params [C, 2] = (x0, kappa)
+    -> (W [C, n_bins], Slog_birth [C], Slog_death [C]) with s_i = 1 / (1 + exp(-kappa (x_i - x0))), W_b = sum_i s_i e_ib and
+    Slog the sum of log s_i over the births / deaths bin_unit_events counts.  out: the triple of an earlier call."""
+    torch = _torch()
+    lib = _hip.load()
+    ts = _dev(ts, torch.float64)
+    te, x = _dev(te, torch.float64, ts.device), _dev(x, torch.float64, ts.device)
+    params = _dev(params, torch.float64, ts.device).reshape(-1, 2)
+    n, C = ts.numel(), int(params.shape[0])
+    if te.numel() != n or x.numel() != n:
+        raise ValueError("ts, te and x differ in length")
+    W, sb, sd = _ade_out(out, ((max(C, 0), max(int(n_bins), 0)), (max(C, 0),), (max(C, 0),)), (torch.float64,) * 3, ts.device,
+                         "(W, Slog_birth, Slog_death)")
+    nbytes = lib.lr_trait_weights_workspace_bytes(n, int(n_bins), C)
+    if nbytes < 0:
+        _hip.check(int(nbytes), "lr_trait_weights_workspace_bytes")
+    ws = alloc_workspace(nbytes, ts.device)
+    prob = _hip.TraitWeightsProblem(_hip.ptr(ts), _hip.ptr(te), _hip.ptr(x), _hip.ptr(params), _hip.ptr(W), _hip.ptr(sb), _hip.ptr(sd),
+                                    _hip.ptr(ws), ws.numel(), n, float(t0), int(n_bins), C, None)
+    _hip.check(_hip.launch_problem(lib.lr_trait_weights, ts.device, prob), "lr_trait_weights")
+    return W, sb, sd
+
+
+TRAIT_SCALARS = {"x0_l": 0, "kappa_l": 1, "x0_m": 2, "kappa_m": 3, "SlogL": 4, "SlogM": 5, "proposed_l": 6, "accepted_l": 7,
+                 "proposed_m": 8, "accepted_m": 9}
+TRAIT_ROW_TAIL = ("x0_l", "kappa_l", "x0_m", "kappa_m", "SlogL", "SlogM", "accepted_l", "accepted_m")
+TraitSettings = namedtuple("TraitSettings", "const_rates const_death_rate use_rate_HP poisson_HP update_fraction trait_every "
+                           "win_x0 win_kappa x0_lo x0_hi", defaults=(0, 0, 1, 0.0, 0.75, 10, (0.5, 0.5), (0.1, 0.1), -10.0, 10.0))
+
+
+class TraitData:
+    """What every lr_trait_* call of one run shares: the lineages with their traits on the device, the unit-bin event counts
+    as doubles, the window and the warning word."""
+
+    def __init__(self, ts, te, x, t0, n_bins, start_time=None, end_time=None, device=None):
+        torch = _torch()
+        self.ts = _dev(ts, torch.float64, device)
+        self.device = self.ts.device
+        self.te, self.x = _dev(te, torch.float64, self.device), _dev(x, torch.float64, self.device)
+        self.n, self.t0, self.n_bins = int(self.ts.numel()), float(t0), int(n_bins)
+        if self.te.numel() != self.n or self.x.numel() != self.n:
+            raise ValueError("ts, te and x differ in length")
+        sp, ex, _ = bin_unit_events(self.ts, self.te, self.t0, self.n_bins)
+        self.sp, self.ex = sp.to(torch.float64), ex.to(torch.float64)
+        self.start_time = float(self.ts.min().item()) if start_time is None else float(start_time)
+        self.end_time = float(self.te.max().item()) if end_time is None else float(end_time)
+        self.warn = torch.zeros(1, dtype=torch.int32, device=self.device)
+
+    def warnings(self):
+        return int(self.warn.item())
+
+
+def trait_problem(data, state, ws, n_chains, seed, settings=TraitSettings(), chain0=0):
+    """The descriptor of a call (_hip.TraitProblem; it refers to the tensors of data, state and ws: keep them alive)."""
+    st = settings
+    two = _hip.c_f64 * 2
+    return _hip.TraitProblem(_hip.ptr(data.ts), _hip.ptr(data.te), _hip.ptr(data.x), _hip.ptr(data.sp), _hip.ptr(data.ex),
+                             _hip.ptr(state), _hip.ptr(data.warn), _hip.ptr(ws), 0 if ws is None else ws.numel(), data.n, int(chain0),
+                             data.t0, data.start_time, data.end_time, float(st.poisson_HP), float(st.update_fraction),
+                             two(*[float(v) for v in st.win_x0]), two(*[float(v) for v in st.win_kappa]), float(st.x0_lo),
+                             float(st.x0_hi), data.n_bins, int(n_chains), int(st.const_rates), int(st.const_death_rate),
+                             int(st.use_rate_HP), int(st.trait_every), int(seed) & 0xFFFFFFFFFFFFFFFF, None)
+
+
+def _trait_ws(data, n_chains):
+    lib = _hip.load()
+    nbytes = lib.lr_trait_workspace_bytes(data.n, data.n_bins, int(n_chains))
+    if nbytes < 0:
+        _hip.check(int(nbytes), "lr_trait_workspace_bytes")
+    return alloc_workspace(nbytes, data.device)
+
+
+def trait_init(data, n_chains, seed, settings=TraitSettings(), chain0=0, params0=None, out=None):
+    """The initial state of every chain (lr_trait_init) -> state [C, LR_TRAIT_STATE_W]: lr_rjbin's rows, then the trait
+    scalars (TRAIT_SCALARS) and the chain's WL, WM.  params0 [C, 4] = (x0_l, kappa_l, x0_m, kappa_m); None: zeros."""
+    torch = _torch()
+    lib = _hip.load()
+    C = int(n_chains)
+    (state,) = _ade_out(out, ((max(C, 0), _hip.LR_TRAIT_STATE_W),), (torch.float64,), data.device, "(state,)")
+    p0 = None
+    if params0 is not None:
+        p0 = _dev(params0, torch.float64, data.device).reshape(-1)
+        if p0.numel() != 4 * C:
+            raise ValueError("params0 [C, 4]")
+    ws = _trait_ws(data, C)
+    rc = _hip.launch_problem(lib.lr_trait_init, data.device, trait_problem(data, state, ws, C, seed, settings, chain0), _hip.ptr(p0))
+    _hip.check(rc, "lr_trait_init")
+    return state
+
+
+def trait_steps(data, state, it0, n_iters, s_freq, seed, settings=TraitSettings(), chain0=0, rows=None, slot0=0, out=None):
+    """Iterations it0 .. it0 + n_iters - 1 of every chain of `state` (updated in place; lr_trait_steps) -> rows [cap, C,
+    LR_TRAIT_ROW_W]: the engines' trace row, then TRAIT_ROW_TAIL.  rows / slot0 as rjbin_steps."""
+    torch = _torch()
+    lib = _hip.load()
+    if state.dtype != torch.float64 or state.dim() != 2 or state.shape[1] != _hip.LR_TRAIT_STATE_W or not state.is_contiguous() \
+            or state.device != data.device:
+        raise ValueError("state must be trait_init's [C, LR_TRAIT_STATE_W] float64 tensor on the data's device")
+    C = int(state.shape[0])
+    n = rows_due(it0, n_iters, s_freq) if int(s_freq) >= 1 and int(n_iters) >= 0 and int(it0) >= 0 else 0
+    if rows is None:
+        (rows,) = _ade_out(out, ((max(n, 0), C, _hip.LR_TRAIT_ROW_W),), (torch.float64,), data.device, "(rows,)")
+    elif rows.dtype != torch.float64 or rows.dim() != 3 or not rows.is_contiguous() or rows.device != data.device \
+            or tuple(rows.shape[1:]) != (C, _hip.LR_TRAIT_ROW_W):
+        raise ValueError("rows must be a [cap, C, LR_TRAIT_ROW_W] float64 tensor on the data's device")
+    ws = _trait_ws(data, C)
+    rc = _hip.launch_problem(lib.lr_trait_steps, data.device, trait_problem(data, state, ws, C, seed, settings, chain0), int(it0),
+                             int(n_iters), int(s_freq), _hip.ptr(rows) if rows.numel() else None, int(rows.shape[0]), int(slot0))
+    _hip.check(rc, "lr_trait_steps")
+    return rows
+
+
+class TraitEngine:
+    """C chains of the trait-dependent RJ sampler on one data set, in the style of replicates.ReplicateEngine: the trace
+    [n_trace_slots, C, LR_TRAIT_ROW_W] is resident; its first LR_TRACE_W columns have the engines' row layout."""
+
+    def __init__(self, ts, te, x, n_chains, t0=None, n_bins=None, seed=1, settings=TraitSettings(), s_freq=1000, n_trace_slots=0,
+                 chain_offset=0, device=None):
+        torch = _torch()
+        ts_h, te_h = _host_f64(ts), _host_f64(te)
+        self.t0 = float(np.floor(ts_h.min())) if t0 is None else float(t0)
+        self.n_bins = int(np.ceil(te_h.max()) - self.t0) if n_bins is None else int(n_bins)
+        self.data = TraitData(ts, te, x, self.t0, self.n_bins, float(ts_h.min()), float(te_h.max()), device)
+        self.device = self.data.device
+        self.settings, self.seed, self.chain_offset = settings, int(seed), int(chain_offset)
+        self.n_chains, self.s_freq, self.n_trace_slots = int(n_chains), int(s_freq), int(n_trace_slots)
+        self.start_time, self.end_time = self.data.start_time, self.data.end_time
+        self.trace = alloc_output((self.n_trace_slots, self.n_chains, _hip.LR_TRAIT_ROW_W), torch.float64, self.device, zero=True)
+        self.state = None
+        self.iterations = 0
+
+    def init(self, params0=None):
+        self.data.warn.zero_()
+        self.state = trait_init(self.data, self.n_chains, self.seed, self.settings, self.chain_offset, params0)
+        self.iterations = 0
+
+    def samples_done(self):
+        return min(self.n_trace_slots, (self.iterations + self.s_freq - 1) // self.s_freq)
+
+    def steps(self, n):
+        if self.state is None:
+            raise _hip.HipLibraryError("TraitEngine.steps before init")
+        n = int(n)
+        due = rows_due(self.iterations, n, self.s_freq) if n > 0 else 0
+        slot0 = (self.iterations + self.s_freq - 1) // self.s_freq
+        if slot0 + due > self.n_trace_slots:
+            raise ValueError("the trace holds %d samples; %d iterations from %d on sample up to row %d" %
+                             (self.n_trace_slots, n, self.iterations, slot0 + due))
+        trait_steps(self.data, self.state, self.iterations, n, self.s_freq, self.seed, self.settings, self.chain_offset,
+                    rows=self.trace, slot0=slot0)
+        self.iterations += n
+
+    def set_windows(self, win_x0, win_kappa):
+        """the sliding windows of the trait move, per side (tuned on the host between blocks during the burn-in)"""
+        self.settings = self.settings._replace(win_x0=tuple(win_x0), win_kappa=tuple(win_kappa))
+
+    def trait_counts(self):
+        """(proposed [C, 2], accepted [C, 2]) trait moves so far, per side (a device read-back)"""
+        sc = self.state[:, _hip.LR_TRAIT_ROW_SCALARS:_hip.LR_TRAIT_ROW_SCALARS + 10].cpu().numpy()
+        return sc[:, [6, 8]], sc[:, [7, 9]]
+
+    def check_status(self):
+        import torch
+        torch.cuda.synchronize(self.device)
+
+    def warnings(self):
+        return self.data.warnings()
+
+    def trace_rows(self):
+        """the rows written so far, on the host: [samples, C, LR_TRAIT_ROW_W]"""
+        return self.trace[:self.samples_done()].cpu().numpy()
+
+    def close(self):
+        self.state = None
+
+
 def ess_summary(rows, n_samples, columns, burnin=0.1, max_lag=2000):
     """Convergence summary of rows [>= n_samples, C, width] (lr_ess_summary): per chain and column Tracer's ESS, ACT,
     SE of the mean and the lag its sum stopped at, and per column the pooled mean, the pooled ESS and the split R-hat.
