@@ -1,6 +1,6 @@
 """ctypes binding of libliterate_hip.so (include/literate_hip.h, include/literate_hip_age.h, include/literate_hip_ade.h,
 include/literate_hip_adej.h, include/literate_hip_mlik.h, include/literate_hip_tmlik.h, include/literate_hip_rjbin.h, include/literate_hip_rjmc3.h,
-include/literate_hip_parbin.h, include/literate_hip_score.h, include/literate_hip_abc.h, include/literate_hip_trait.h).  Fails loudly:
+include/literate_hip_parbin.h, include/literate_hip_score.h, include/literate_hip_abc.h, include/literate_hip_trait.h, include/literate_hip_mte.h).  Fails loudly:
 no fallback."""
 import ctypes as C
 import os
@@ -30,6 +30,8 @@ LR_ABC_FLAG_OVERFLOW, LR_ABC_FLAG_EXTINCT, LR_ABC_FLAG_REFUSED = 1, 2, 4
 LR_TRAIT_F, LR_TRAIT_MAX_N, LR_TRAIT_CB, LR_TRAIT_TILE, LR_TRAIT_MAX_TILES = 38, 1 << 24, 8, 2048, 1024
 LR_P_TRAIT_MOVE, LR_P_TRAIT_ACCEPT = 60, 61
 LR_TRAIT_ROW_SCALARS, LR_TRAIT_ROW_WL, LR_TRAIT_ROW_WM, LR_TRAIT_STATE_W = 448, 512, 1024, 1536
+# include/literate_hip_mte.h
+LR_MTE_MAX_TRAITS, LR_MTE_MAX_STATES, LR_MTE_MAX_CATS, LR_MTE_MAX_COMBOS, LR_MTE_STATE_W, LR_MTE_ROW_W = 16, 16, 128, 1024, 176, 192
 LR_WARN_KCAP = 2
 LR_STATE_ROWS, LR_ISTATE_ROWS = 9, 5
 LR_TRACE_HEAD = 13
@@ -133,8 +135,15 @@ class TraitProblem(C.Structure):
                 ("trait_every", c_i32), ("seed", C.c_uint64), ("stream", c_vp)]
 
 
+class MteProblem(C.Structure):
+    """lr_mte_problem (include/literate_hip_mte.h): the descriptor both lr_mte_* entry points take; the stream rides in it"""
+    _fields_ = [("code", c_vp), ("n_states", c_vp), ("n_states_host", c_vp), ("n", c_vp), ("E", c_vp), ("B", c_vp), ("state", c_vp),
+                ("G", c_i32), ("T", c_i32), ("P", c_i32), ("chains_per_problem", c_i32), ("bvs", c_i32), ("constant", c_i32),
+                ("bvs_from", c_i64), ("pI", c_f64), ("chain0", c_i64), ("seed", C.c_uint64), ("stream", c_vp)]
+
+
 # name -> (restype, argtypes); exactly the symbols include/literate_hip.h, literate_hip_age.h, literate_hip_ade.h and
-# literate_hip_adej.h, literate_hip_mlik.h, literate_hip_tmlik.h, literate_hip_rjbin.h, literate_hip_rjmc3.h, literate_hip_parbin.h, literate_hip_score.h, literate_hip_abc.h, literate_hip_trait.h declare (+ the RNG debug hook)
+# literate_hip_adej.h, literate_hip_mlik.h, literate_hip_tmlik.h, literate_hip_rjbin.h, literate_hip_rjmc3.h, literate_hip_parbin.h, literate_hip_score.h, literate_hip_abc.h, literate_hip_trait.h, literate_hip_mte.h declare (+ the RNG debug hook)
 SIGNATURES = {
     "lr_version": (c_i32, []),
     "lr_bin_events_workspace_bytes": (c_i64, [c_i64, c_i32]),
@@ -209,6 +218,8 @@ SIGNATURES = {
     "lr_trait_workspace_bytes": (c_i64, [c_i64, c_i32, c_i32]),
     "lr_trait_init": (c_i32, [C.POINTER(TraitProblem), c_vp]),
     "lr_trait_steps": (c_i32, [C.POINTER(TraitProblem), c_i64, c_i64, c_i32, c_vp, c_i64, c_i64]),
+    "lr_mte_init": (c_i32, [C.POINTER(MteProblem), c_i32]),
+    "lr_mte_steps": (c_i32, [C.POINTER(MteProblem), c_i64, c_i64, c_i32, c_vp, c_i64, c_i64]),
     "lr_ess_summary_workspace_bytes": (c_i64, [c_i32, c_i32, c_i32, c_vp, c_i32, c_f64, c_i32]),
     "lr_ess_summary": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_i32, c_f64, c_i32, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
     "lr_col_summary_workspace_bytes": (c_i64, [c_i32, c_i32, c_i32, c_vp, c_i32, c_f64, c_i32, c_i32]),
@@ -294,7 +305,7 @@ def launch(fn, device, *args):
 
 
 def launch_problem(fn, device, problem, *args):
-    """Call an entry point that takes a descriptor with the stream in it (lr_tmlik_*, lr_rjbin_*, lr_rjmc3_*, lr_parbin_*, lr_rtt_score, lr_abc_*, lr_trait_*): `device`'s current torch stream is put
+    """Call an entry point that takes a descriptor with the stream in it (lr_tmlik_*, lr_rjbin_*, lr_rjmc3_*, lr_parbin_*, lr_rtt_score, lr_abc_*, lr_trait_*, lr_mte_*): `device`'s current torch stream is put
     into problem.stream, `device` made current for the call."""
     import torch
     with torch.cuda.device(device):

@@ -1415,6 +1415,179 @@ def parbin_steps(data, state, it0, n_iters, s_freq, seed, settings=ParbinSetting
     return rows
 
 
+MTE_STATE = {"m": 0, "beta_hp": 1, "lik": 2, "prior": 3, "proposed": 4, "accepted": 7, "I": 16, "sd": 32, "Y": 48}
+MTE_MOVES = ("Y", "m", "indicator")
+# bvs: Bayesian variable selection (-bvs); constant: only m moves (-const 1); bvs_from: the first iteration an indicator may flip
+# at (the reference's `iteration > 1000`); pI: the prior probability of an indicator
+MteSettings = namedtuple("MteSettings", "bvs constant bvs_from pI", defaults=(1, 0, 1001, 0.05))
+
+
+def mte_row_columns(n_states):
+    """where a row of lr_mte_steps keeps what: {"I": slice, "q": slice, "sd": slice, "beta_hp": int, "width": int} (it, posterior,
+    likelihood, prior, m are columns 0 .. 4)"""
+    T, nc = len(n_states), int(np.sum(n_states))
+    return {"I": slice(5, 5 + T), "q": slice(5 + T, 5 + T + nc), "sd": slice(5 + T + nc, 5 + 2 * T + nc), "beta_hp": 5 + 2 * T + nc,
+            "width": 6 + 2 * T + nc}
+
+
+def mte_slice(ts, te, t0, t1):
+    """The time slice (t0, t1], t0 > t1 in time before the present (MTEmodel.py:145-155): the lineages with te < t0 and ts > t1,
+    ts clipped to t0, both times shifted by -t1, te <= 0 set to 0 (extant in the slice) -> (kept [n] bool, bl, ex of the kept)"""
+    ts, te = np.asarray(ts, dtype=np.float64), np.asarray(te, dtype=np.float64)
+    kept = (te < t0) & (ts > t1)
+    s, e = np.minimum(ts[kept], t0) - t1, te[kept] - t1
+    e = np.where(e <= 0, 0.0, e)
+    return kept, s - e, (e > 0).astype(np.float64)
+
+
+def mte_tables(ts, te, traits, slices):
+    """The sufficient statistics of the multi-trait extinction model, in numpy: traits [n, T] of any sortable values; slices
+    [(t0, t1)].  The states of a column are its distinct values in the WHOLE table, mapped in sorted order to 0 .. S_t - 1; the
+    combinations are the distinct rows of the mapped table, in lexicographic order, shared by all slices.
+    -> {"code" [G, T] uint8, "n_states" [T] int32, "states" [per trait the sorted values], "combo" [n] (the combination of every
+    lineage), "n", "E", "B" [P, G] float64 (lineages, extinctions, lineage-time per slice and combination)}"""
+    traits = np.asarray(traits)
+    if traits.ndim == 1:
+        traits = traits.reshape(-1, 1)
+    n_lin, T = traits.shape
+    states, mapped = [], np.zeros((n_lin, T), dtype=np.int64)
+    for t in range(T):
+        u, inv = np.unique(traits[:, t], return_inverse=True)
+        states.append(u)
+        mapped[:, t] = inv.reshape(-1)
+    code, combo = np.unique(mapped, axis=0, return_inverse=True)
+    combo = combo.reshape(-1)
+    G, P = code.shape[0], len(slices)
+    n, E, B = np.zeros((P, G)), np.zeros((P, G)), np.zeros((P, G))
+    for p, (t0, t1) in enumerate(slices):
+        kept, bl, ex = mte_slice(ts, te, t0, t1)
+        g = combo[kept]
+        n[p] = np.bincount(g, minlength=G)
+        E[p] = np.bincount(g, weights=ex, minlength=G)
+        B[p] = np.bincount(g, weights=bl, minlength=G)
+    return {"code": code.astype(np.uint8) if code.max(initial=0) < 256 else code, "n_states": np.array([len(u) for u in states], dtype=np.int32),
+            "states": states, "combo": combo, "n": n, "E": E, "B": B}
+
+
+class MteData:
+    """What every lr_mte_* call of one run shares (include/literate_hip_mte.h): code [G, T] uint8 and n_states [T] int32 with
+    its host copy, n, E, B [P, G] float64 - device tensors -, the traits' names and the slices' bounds.  Chain c belongs to
+    problem c // chains_per_problem.  Host arrays are checked here (a code must lie below its trait's number of states);
+    device tensors are used as they are, with n_states_host given beside them."""
+
+    def __init__(self, code, n_states, n, E, B, chains_per_problem=1, names=None, slices=None, n_states_host=None, device=None):
+        torch = _torch()
+        if n_states_host is None:
+            n_states_host = n_states.cpu().numpy() if hasattr(n_states, "cpu") else n_states
+        self.n_states_host = np.ascontiguousarray(np.asarray(n_states_host, dtype=np.int32).reshape(-1))
+        if not hasattr(code, "is_cuda"):
+            code = np.asarray(code)
+            if code.ndim != 2 or code.shape[1] != self.n_states_host.size or code.shape[0] < 1:
+                raise ValueError("code must be [G, T] with one column per entry of n_states")
+            if (code < 0).any() or (code >= self.n_states_host[None, :]).any():
+                raise ValueError("a code lies outside 0 .. S_t - 1 of its trait")
+        self.code = _dev(code, torch.uint8, device)
+        self.device = self.code.device
+        self.n_states = _dev(n_states, torch.int32, self.device).reshape(-1)
+        self.G, self.T = int(self.code.shape[0]), int(self.code.shape[1]) if self.code.dim() == 2 else 0
+        two = lambda x: _dev(x, torch.float64, self.device).reshape(-1, self.G)
+        self.n, self.E, self.B = two(n), two(E), two(B)
+        self.P = int(self.n.shape[0])
+        if self.code.dim() != 2 or self.n_states.numel() != self.T or self.n_states_host.size != self.T \
+                or any(tuple(t.shape) != (self.P, self.G) for t in (self.E, self.B)):
+            raise ValueError("shape mismatch: code [G, T]; n_states [T]; n, E, B [P, G]")
+        self.n_cats = int(self.n_states_host.sum())
+        self.chains_per_problem = int(chains_per_problem)
+        self.n_chains = self.P * self.chains_per_problem
+        self.names = list(names) if names is not None else ["t%d" % t for t in range(self.T)]
+        self.slices = list(slices) if slices is not None else [(np.inf, 0.0)] * self.P
+
+    @classmethod
+    def from_lineages(cls, ts, te, traits, slices, chains_per_problem=1, names=None, device=None):
+        """the slicing, state mapping and grouping of mte_tables, uploaded; the tables stay in .tables"""
+        tab = mte_tables(ts, te, traits, slices)
+        if tab["code"].dtype != np.uint8:
+            raise ValueError("a trait with more than 255 states")
+        data = cls(tab["code"], tab["n_states"], tab["n"], tab["E"], tab["B"], chains_per_problem, names, slices, device=device)
+        data.tables = tab
+        return data
+
+
+def mte_problem(data, state, seed, settings=MteSettings(), chain0=0):
+    """The descriptor of a call (_hip.MteProblem; it refers to the tensors of data and state and to data.n_states_host: keep
+    them alive while it is used)."""
+    st = settings
+    return _hip.MteProblem(_hip.ptr(data.code), _hip.ptr(data.n_states), data.n_states_host.ctypes.data_as(_hip.c_vp), _hip.ptr(data.n),
+                           _hip.ptr(data.E), _hip.ptr(data.B), _hip.ptr(state), data.G, data.T, data.P, data.chains_per_problem,
+                           int(st.bvs), int(st.constant), int(st.bvs_from), float(st.pI), int(chain0), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                           None)
+
+
+def mte_state(data, m, Y, I, sd=None, beta_hp=1.0):
+    """A host state [C, LR_MTE_STATE_W] holding the parameters of every chain, for mte_init(given=...): m [C]; Y [C, sum S_t],
+    the traits concatenated; I [C, T]; sd [C, T] (1 where not given); beta_hp [C] or a number.  Likelihood, prior and counters 0."""
+    C, S = data.n_chains, MTE_STATE
+    st = np.zeros((C, _hip.LR_MTE_STATE_W))
+    st[:, S["m"]] = np.broadcast_to(np.asarray(m, dtype=np.float64), (C,))
+    st[:, S["beta_hp"]] = np.broadcast_to(np.asarray(beta_hp, dtype=np.float64), (C,))
+    st[:, S["I"]:S["I"] + data.T] = np.broadcast_to(np.asarray(I, dtype=np.float64), (C, data.T))
+    st[:, S["sd"]:S["sd"] + data.T] = 1.0 if sd is None else np.broadcast_to(np.asarray(sd, dtype=np.float64), (C, data.T))
+    st[:, S["Y"]:S["Y"] + data.n_cats] = np.broadcast_to(np.asarray(Y, dtype=np.float64), (C, data.n_cats))
+    return st
+
+
+def mte_init(data, seed, settings=MteSettings(), chain0=0, given=None, out=None):
+    """The initial state of every chain (lr_mte_init) -> state [C, LR_MTE_STATE_W] (elements: MTE_STATE).  given: a state whose
+    m, beta_hp, I, sd and Y the caller wrote (mte_state): they are kept, and their likelihood, prior and zeroed counters
+    added."""
+    torch = _torch()
+    lib = _hip.load()
+    (state,) = _ade_out(out, ((max(data.n_chains, 0), _hip.LR_MTE_STATE_W),), (torch.float64,), data.device, "(state,)")
+    if given is not None:
+        g = _dev(given, torch.float64, data.device)
+        if tuple(g.shape) != tuple(state.shape):
+            raise ValueError("given must be a [C, LR_MTE_STATE_W] state")
+        state.copy_(g)
+    rc = _hip.launch_problem(lib.lr_mte_init, data.device, mte_problem(data, state, seed, settings, chain0), 0 if given is None else 1)
+    _hip.check(rc, "lr_mte_init")
+    return state
+
+
+def mte_steps(data, state, it0, n_iters, s_freq, seed, settings=MteSettings(), chain0=0, rows=None, slot0=0, out=None):
+    """Iterations it0 .. it0 + n_iters - 1 of every chain of `state` (updated in place; lr_mte_steps) -> rows [cap, C,
+    LR_MTE_ROW_W] (columns: mte_row_columns).  rows: an earlier call's buffer to go on writing into at slot `slot0`; otherwise a
+    fresh one of exactly the rows due."""
+    torch = _torch()
+    lib = _hip.load()
+    C = data.n_chains
+    if state.dtype != torch.float64 or tuple(state.shape) != (C, _hip.LR_MTE_STATE_W) or not state.is_contiguous() \
+            or state.device != data.device:
+        raise ValueError("state must be mte_init's [C, LR_MTE_STATE_W] float64 tensor on the data's device")
+    n = rows_due(it0, n_iters, s_freq) if int(s_freq) >= 1 and int(n_iters) >= 0 and int(it0) >= 0 else 0
+    if rows is None:
+        (rows,) = _ade_out(out, ((max(n, 0), C, _hip.LR_MTE_ROW_W),), (torch.float64,), data.device, "(rows,)")
+    elif rows.dtype != torch.float64 or rows.dim() != 3 or not rows.is_contiguous() or rows.device != data.device \
+            or tuple(rows.shape[1:]) != (C, _hip.LR_MTE_ROW_W):
+        raise ValueError("rows must be a [cap, C, LR_MTE_ROW_W] float64 tensor on the data's device")
+    rc = _hip.launch_problem(lib.lr_mte_steps, data.device, mte_problem(data, state, seed, settings, chain0), int(it0), int(n_iters),
+                             int(s_freq), _hip.ptr(rows) if rows.numel() else None, int(rows.shape[0]), int(slot0))
+    _hip.check(rc, "lr_mte_steps")
+    return rows
+
+
+def mte_run(data, n_iter, s_freq, seed, settings=MteSettings(), chain0=0):
+    """mte_init, then iterations 0 .. n_iter - 1 in one launch -> (rows, state)"""
+    state = mte_init(data, seed, settings, chain0)
+    return mte_steps(data, state, 0, n_iter, s_freq, seed, settings, chain0), state
+
+
+def mte_loglik(data, m, Y, I, sd=None, beta_hp=1.0, settings=MteSettings()):
+    """The log-likelihood and log prior of given parameters, one set per chain (lr_mte_init with given = 1; arguments as
+    mte_state's) -> (lik [C], prior [C]), device tensors"""
+    state = mte_init(data, 0, settings, given=mte_state(data, m, Y, I, sd, beta_hp))
+    return state[:, MTE_STATE["lik"]].clone(), state[:, MTE_STATE["prior"]].clone()
+
+
 def rjmc3_problem(data, state, swaps, seed, betas, swap_every=0, settings=RjbinSettings(), chain0=0):
     """The descriptor of a call on temperature ladders (_hip.Rjmc3Problem; it refers to the tensors of data, state and swaps
     and holds the host array of the betas: keep them alive while it is used).  betas: host floats [T], betas[0] = 1."""
