@@ -1,6 +1,7 @@
 """ctypes binding of libliterate_hip.so (include/literate_hip.h, include/literate_hip_age.h, include/literate_hip_ade.h,
 include/literate_hip_adej.h, include/literate_hip_mlik.h, include/literate_hip_tmlik.h, include/literate_hip_rjbin.h, include/literate_hip_rjmc3.h,
-include/literate_hip_parbin.h, include/literate_hip_score.h, include/literate_hip_abc.h, include/literate_hip_trait.h, include/literate_hip_mte.h).  Fails loudly:
+include/literate_hip_parbin.h, include/literate_hip_score.h, include/literate_hip_abc.h, include/literate_hip_trait.h, include/literate_hip_mte.h,
+include/literate_hip_mtrend.h).  Fails loudly:
 no fallback."""
 import ctypes as C
 import os
@@ -32,6 +33,8 @@ LR_P_TRAIT_MOVE, LR_P_TRAIT_ACCEPT = 60, 61
 LR_TRAIT_ROW_SCALARS, LR_TRAIT_ROW_WL, LR_TRAIT_ROW_WM, LR_TRAIT_STATE_W = 448, 512, 1024, 1536
 # include/literate_hip_mte.h
 LR_MTE_MAX_TRAITS, LR_MTE_MAX_STATES, LR_MTE_MAX_CATS, LR_MTE_MAX_COMBOS, LR_MTE_STATE_W, LR_MTE_ROW_W = 16, 16, 128, 1024, 176, 192
+# include/literate_hip_mtrend.h
+LR_MTREND_MAX_BINS, LR_MTREND_MAX_COVS, LR_MTREND_STATE_W, LR_MTREND_ROW_W, LR_MTREND_MOVES = 512, 16, 96, 72, 6
 LR_WARN_KCAP = 2
 LR_STATE_ROWS, LR_ISTATE_ROWS = 9, 5
 LR_TRACE_HEAD = 13
@@ -142,8 +145,16 @@ class MteProblem(C.Structure):
                 ("bvs_from", c_i64), ("pI", c_f64), ("chain0", c_i64), ("seed", C.c_uint64), ("stream", c_vp)]
 
 
+class MtrendProblem(C.Structure):
+    """lr_mtrend_problem (include/literate_hip_mtrend.h): the descriptor both lr_mtrend_* entry points take; the stream rides in it"""
+    _fields_ = [("n_spec", c_vp), ("n_exti", c_vp), ("DT", c_vp), ("X", c_vp), ("sx_spec", c_vp), ("sx_exti", c_vp), ("state", c_vp),
+                ("n_bins", c_i32), ("P", c_i32), ("C", c_i32), ("m_birth", c_i32), ("m_death", c_i32), ("no_death", c_i32),
+                ("bvs", c_i32), ("reserved", c_i32), ("bvs_from", c_i64), ("pI", c_f64), ("slab_sd", c_f64), ("win", c_f64 * 2),
+                ("chain0", c_i64), ("seed", C.c_uint64), ("stream", c_vp)]
+
+
 # name -> (restype, argtypes); exactly the symbols include/literate_hip.h, literate_hip_age.h, literate_hip_ade.h and
-# literate_hip_adej.h, literate_hip_mlik.h, literate_hip_tmlik.h, literate_hip_rjbin.h, literate_hip_rjmc3.h, literate_hip_parbin.h, literate_hip_score.h, literate_hip_abc.h, literate_hip_trait.h, literate_hip_mte.h declare (+ the RNG debug hook)
+# literate_hip_adej.h, literate_hip_mlik.h, literate_hip_tmlik.h, literate_hip_rjbin.h, literate_hip_rjmc3.h, literate_hip_parbin.h, literate_hip_score.h, literate_hip_abc.h, literate_hip_trait.h, literate_hip_mte.h, literate_hip_mtrend.h declare (+ the RNG debug hook)
 SIGNATURES = {
     "lr_version": (c_i32, []),
     "lr_bin_events_workspace_bytes": (c_i64, [c_i64, c_i32]),
@@ -220,6 +231,8 @@ SIGNATURES = {
     "lr_trait_steps": (c_i32, [C.POINTER(TraitProblem), c_i64, c_i64, c_i32, c_vp, c_i64, c_i64]),
     "lr_mte_init": (c_i32, [C.POINTER(MteProblem), c_i32]),
     "lr_mte_steps": (c_i32, [C.POINTER(MteProblem), c_i64, c_i64, c_i32, c_vp, c_i64, c_i64]),
+    "lr_mtrend_init": (c_i32, [C.POINTER(MtrendProblem), c_i32]),
+    "lr_mtrend_steps": (c_i32, [C.POINTER(MtrendProblem), c_i64, c_i64, c_i32, c_vp, c_i64, c_i64]),
     "lr_ess_summary_workspace_bytes": (c_i64, [c_i32, c_i32, c_i32, c_vp, c_i32, c_f64, c_i32]),
     "lr_ess_summary": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_i32, c_f64, c_i32, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
     "lr_col_summary_workspace_bytes": (c_i64, [c_i32, c_i32, c_i32, c_vp, c_i32, c_f64, c_i32, c_i32]),
@@ -305,7 +318,7 @@ def launch(fn, device, *args):
 
 
 def launch_problem(fn, device, problem, *args):
-    """Call an entry point that takes a descriptor with the stream in it (lr_tmlik_*, lr_rjbin_*, lr_rjmc3_*, lr_parbin_*, lr_rtt_score, lr_abc_*, lr_trait_*, lr_mte_*): `device`'s current torch stream is put
+    """Call an entry point that takes a descriptor with the stream in it (lr_tmlik_*, lr_rjbin_*, lr_rjmc3_*, lr_parbin_*, lr_rtt_score, lr_abc_*, lr_trait_*, lr_mte_*, lr_mtrend_*): `device`'s current torch stream is put
     into problem.stream, `device` made current for the call."""
     import torch
     with torch.cuda.device(device):

@@ -17,7 +17,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(CSRC, "libliterate_hip.so")
 BUILD_INFO = os.path.join(CSRC, "libliterate_hip.build.json")
 OBJ_DIR = os.path.join(CSRC, "_build")
-SOURCES = ["lr_stats.hip", "lr_loglik.hip", "lr_mcmc.hip", "lr_plan.hip", "lr_spec.hip", "lr_stream.hip", "lr_packscan.hip", "lr_pack.hip", "lr_sim.hip", "lr_simbatch.hip", "lr_format.hip", "lr_summary.hip", "lr_prior.hip", "lr_ess.hip", "lr_curves.hip", "lr_waic.hip", "lr_loo.hip", "lr_age.hip", "lr_ade.hip", "lr_adej.hip", "lr_mlik.hip", "lr_tmlik.hip", "lr_rjbin.hip", "lr_rjmc3.hip", "lr_parbin.hip", "lr_score.hip", "lr_abc.hip", "lr_trait.hip", "lr_mte.hip"]
+SOURCES = ["lr_stats.hip", "lr_loglik.hip", "lr_mcmc.hip", "lr_plan.hip", "lr_spec.hip", "lr_stream.hip", "lr_packscan.hip", "lr_pack.hip", "lr_sim.hip", "lr_simbatch.hip", "lr_format.hip", "lr_summary.hip", "lr_prior.hip", "lr_ess.hip", "lr_curves.hip", "lr_waic.hip", "lr_loo.hip", "lr_age.hip", "lr_ade.hip", "lr_adej.hip", "lr_mlik.hip", "lr_tmlik.hip", "lr_rjbin.hip", "lr_rjmc3.hip", "lr_parbin.hip", "lr_score.hip", "lr_abc.hip", "lr_trait.hip", "lr_mte.hip", "lr_mtrend.hip"]
 HEADERS = ["lr_device.h", "lr_math.h", "lr_chain.h", "lr_dd.h", "lr_scan.h", "lr_step.h", "lr_spec.h", "lr_plan.h", "lr_engine.h", "lr_internal.h", "lr_drawwalk.h", "lr_ade_tables.h", "lr_rjbin_iter.h", "lr_par_iter.h", "lr_rtt.h",
            os.path.join("..", "..", "include", "literate_hip.h"), os.path.join("..", "..", "include", "literate_hip_age.h"),
            os.path.join("..", "..", "include", "literate_hip_ade.h"), os.path.join("..", "..", "include", "literate_hip_adej.h"),
@@ -25,7 +25,7 @@ HEADERS = ["lr_device.h", "lr_math.h", "lr_chain.h", "lr_dd.h", "lr_scan.h", "lr
            os.path.join("..", "..", "include", "literate_hip_rjbin.h"), os.path.join("..", "..", "include", "literate_hip_rjmc3.h"),
            os.path.join("..", "..", "include", "literate_hip_parbin.h"), os.path.join("..", "..", "include", "literate_hip_score.h"),
            os.path.join("..", "..", "include", "literate_hip_abc.h"), os.path.join("..", "..", "include", "literate_hip_trait.h"),
-           os.path.join("..", "..", "include", "literate_hip_mte.h")]
+           os.path.join("..", "..", "include", "literate_hip_mte.h"), os.path.join("..", "..", "include", "literate_hip_mtrend.h")]
 # Per translation unit.  The speculative kernel's loop body is ~8000 instructions at a 168-VGPR budget: machine LICM
 # hoists every literal of the inlined log/exp polynomials out of it and the allocator then spills them (592 bytes of
 # scratch, reloaded inside the candidate build); without the pass the kernel keeps 128 bytes and the few-chain shards

@@ -144,7 +144,8 @@ __device__ __forceinline__ int lr_wave_exclusive_scan_i32(int x) {
 #define LR_P_INIT 10
 #define LR_P_SWAP 11   /* the swap uniforms of a temperature ladder (lr_rjmc3.hip), in the stream of the ladder's replica 0 */
 // (purposes defined beside their users: 16-19 lr_dd.h, 24 lr_sim.hip / lr_simbatch.hip, 32-35 lr_dd.h, 40 lr_prior.hip,
-// 41 lr_age.hip, 48-51 lr_adej.hip, 56 lr_abc.hip, 60-61 literate_hip_trait.h, 64-71 literate_hip_mte.h)
+// 41 lr_age.hip, 48-51 lr_adej.hip, 56 lr_abc.hip, 60-61 literate_hip_trait.h, 64-71 literate_hip_mte.h,
+// 72-75 literate_hip_mtrend.h)
 #define LR_GAMMA_MAX_ATTEMPTS 32
 
 struct lr_u2 {

@@ -1588,6 +1588,129 @@ def mte_loglik(data, m, Y, I, sd=None, beta_hp=1.0, settings=MteSettings()):
     return state[:, MTE_STATE["lik"]].clone(), state[:, MTE_STATE["prior"]].clone()
 
 
+MTREND_STATE = {"l0": 0, "m0": 1, "lik_b": 2, "lik_d": 3, "prior": 4, "E_b": 5, "E_d": 6, "proposed": 8, "accepted": 16, "I_l": 32, "a": 48,
+                "I_m": 64, "b": 80}
+# the counters' elements; the last two count the coefficient moves where I_j = 1, what a window is tuned from
+MTREND_MOVES = ("multiplier", "coef_birth", "coef_death", "flip", "coef_birth_included", "coef_death_included")
+# m_birth / m_death: 1 = the side is constant (-const_B / -const_D); no_death: the death side leaves the likelihood; bvs: the
+# indicators flip, from iteration bvs_from on; pI: the prior probability of an indicator; slab_sd: the sd of the Normal prior on
+# a coefficient; win: the sd of a coefficient's step (birth, death)
+MtrendSettings = namedtuple("MtrendSettings", "m_birth m_death no_death bvs bvs_from pI slab_sd win", defaults=(0, 0, 0, 1, 0, 0.1, 1.0, (0.1, 0.1)))
+
+
+def mtrend_row_columns(P):
+    """where a row of lr_mtrend_steps keeps what: {"I_l", "a", "I_m", "b": slices, "width": int} (it, posterior, likelihood,
+    likelihood_birth, likelihood_death, prior, l0, m0 are columns 0 .. 7)"""
+    P = int(P)
+    return {"I_l": slice(8, 8 + P), "a": slice(8 + P, 8 + 2 * P), "I_m": slice(8 + 2 * P, 8 + 3 * P), "b": slice(8 + 3 * P, 8 + 4 * P),
+            "width": 8 + 4 * P}
+
+
+class MtrendData:
+    """What every lr_mtrend_* call of one run shares (include/literate_hip_mtrend.h): n_spec, n_exti, DT [n_bins] and X [P,
+    n_bins] float64 - device tensors -, SX of both sides [P] on the host, the number of chains and the covariates' names.  Host
+    arrays are uploaded and SX is taken from them; device tensors are used as they are (sx = (sx_spec, sx_exti) given beside
+    them spares the read-back)."""
+
+    def __init__(self, n_spec, n_exti, DT, X, n_chains=1, names=None, sx=None, device=None):
+        torch = _torch()
+        if sx is None:
+            ns, ne, Xh = _host_f64(n_spec).reshape(-1), _host_f64(n_exti).reshape(-1), _host_f64(X)
+            Xh = Xh.reshape(-1, ns.size) if ns.size else Xh
+            sx = ((Xh * ns[None, :]).sum(axis=1), (Xh * ne[None, :]).sum(axis=1))
+        self.sx_spec, self.sx_exti = [np.ascontiguousarray(np.asarray(v, dtype=np.float64).reshape(-1)) for v in sx]
+        self.n_spec = _dev(n_spec, torch.float64, device).reshape(-1)
+        self.device = self.n_spec.device
+        self.n_exti, self.DT = _dev(n_exti, torch.float64, self.device).reshape(-1), _dev(DT, torch.float64, self.device).reshape(-1)
+        self.n_bins = int(self.n_spec.numel())
+        self.X = _dev(X, torch.float64, self.device)
+        if self.X.dim() != 2 or self.X.shape[1] != self.n_bins or self.n_exti.numel() != self.n_bins or self.DT.numel() != self.n_bins \
+                or self.sx_spec.size != self.X.shape[0] or self.sx_exti.size != self.X.shape[0]:
+            raise ValueError("shape mismatch: n_spec, n_exti, DT [n_bins]; X [P, n_bins]; sx_spec, sx_exti [P]")
+        self.P = int(self.X.shape[0])
+        self.n_chains = int(n_chains)
+        self.names = list(names) if names is not None else ["x%d" % j for j in range(self.P)]
+
+
+def mtrend_problem(data, state, seed, settings=MtrendSettings(), chain0=0):
+    """The descriptor of a call (_hip.MtrendProblem; it refers to the tensors of data and state and to data's host arrays: keep
+    them alive while it is used)."""
+    st = settings
+    return _hip.MtrendProblem(_hip.ptr(data.n_spec), _hip.ptr(data.n_exti), _hip.ptr(data.DT), _hip.ptr(data.X),
+                              data.sx_spec.ctypes.data_as(_hip.c_vp), data.sx_exti.ctypes.data_as(_hip.c_vp), _hip.ptr(state),
+                              data.n_bins, data.P, data.n_chains, int(st.m_birth), int(st.m_death), int(st.no_death), int(st.bvs), 0,
+                              int(st.bvs_from), float(st.pI), float(st.slab_sd), (_hip.c_f64 * 2)(float(st.win[0]), float(st.win[1])),
+                              int(chain0), int(seed) & 0xFFFFFFFFFFFFFFFF, None)
+
+
+def mtrend_state(data, l0, m0, a, I_l, b, I_m):
+    """A host state [C, LR_MTREND_STATE_W] holding the parameters of every chain, for mtrend_init(given=...): l0, m0 [C] or
+    numbers; a, I_l, b, I_m [C, P] or [P].  Everything else 0."""
+    C, P, S = data.n_chains, data.P, MTREND_STATE
+    st = np.zeros((C, _hip.LR_MTREND_STATE_W))
+    st[:, S["l0"]] = np.broadcast_to(np.asarray(l0, dtype=np.float64), (C,))
+    st[:, S["m0"]] = np.broadcast_to(np.asarray(m0, dtype=np.float64), (C,))
+    for key, v in (("a", a), ("I_l", I_l), ("b", b), ("I_m", I_m)):
+        st[:, S[key]:S[key] + P] = np.broadcast_to(np.asarray(v, dtype=np.float64), (C, P))
+    return st
+
+
+def mtrend_init(data, seed, settings=MtrendSettings(), chain0=0, given=None, out=None):
+    """The initial state of every chain (lr_mtrend_init) -> state [C, LR_MTREND_STATE_W] (elements: MTREND_STATE).  given: a
+    state whose l0, m0, coefficients and indicators the caller wrote (mtrend_state): they are kept, and E, the likelihoods, the
+    prior and zeroed counters added."""
+    torch = _torch()
+    lib = _hip.load()
+    (state,) = _ade_out(out, ((max(data.n_chains, 0), _hip.LR_MTREND_STATE_W),), (torch.float64,), data.device, "(state,)")
+    if given is not None:
+        g = _dev(given, torch.float64, data.device)
+        if tuple(g.shape) != tuple(state.shape):
+            raise ValueError("given must be a [C, LR_MTREND_STATE_W] state")
+        state.copy_(g)
+    rc = _hip.launch_problem(lib.lr_mtrend_init, data.device, mtrend_problem(data, state, seed, settings, chain0), 0 if given is None else 1)
+    _hip.check(rc, "lr_mtrend_init")
+    return state
+
+
+def mtrend_steps(data, state, it0, n_iters, s_freq, seed, settings=MtrendSettings(), chain0=0, rows=None, slot0=0, out=None):
+    """Iterations it0 .. it0 + n_iters - 1 of every chain of `state` (updated in place; lr_mtrend_steps) -> rows [cap, C,
+    LR_MTREND_ROW_W] (columns: mtrend_row_columns).  rows: an earlier call's buffer to go on writing into at slot `slot0`;
+    otherwise a fresh one of exactly the rows due."""
+    torch = _torch()
+    lib = _hip.load()
+    C = data.n_chains
+    if state.dtype != torch.float64 or tuple(state.shape) != (C, _hip.LR_MTREND_STATE_W) or not state.is_contiguous() \
+            or state.device != data.device:
+        raise ValueError("state must be mtrend_init's [C, LR_MTREND_STATE_W] float64 tensor on the data's device")
+    n = rows_due(it0, n_iters, s_freq) if int(s_freq) >= 1 and int(n_iters) >= 0 and int(it0) >= 0 else 0
+    if rows is None:
+        (rows,) = _ade_out(out, ((max(n, 0), C, _hip.LR_MTREND_ROW_W),), (torch.float64,), data.device, "(rows,)")
+    elif rows.dtype != torch.float64 or rows.dim() != 3 or not rows.is_contiguous() or rows.device != data.device \
+            or tuple(rows.shape[1:]) != (C, _hip.LR_MTREND_ROW_W):
+        raise ValueError("rows must be a [cap, C, LR_MTREND_ROW_W] float64 tensor on the data's device")
+    rc = _hip.launch_problem(lib.lr_mtrend_steps, data.device, mtrend_problem(data, state, seed, settings, chain0), int(it0), int(n_iters),
+                             int(s_freq), _hip.ptr(rows) if rows.numel() else None, int(rows.shape[0]), int(slot0))
+    _hip.check(rc, "lr_mtrend_steps")
+    return rows
+
+
+def mtrend_run(data, n_iter, s_freq, seed, settings=MtrendSettings(), chain0=0):
+    """mtrend_init, then iterations 0 .. n_iter - 1 in one launch -> (rows, state)"""
+    state = mtrend_init(data, seed, settings, chain0)
+    return mtrend_steps(data, state, 0, n_iter, s_freq, seed, settings, chain0), state
+
+
+def mtrend_loglik(data, l0, m0, a, I_l, b, I_m, settings=MtrendSettings()):
+    """The log-likelihoods and log prior of given parameters, one set per chain (lr_mtrend_init with given = 1; arguments as
+    mtrend_state's) -> (lik [C], lik_birth [C], lik_death [C], prior [C]), device tensors; lik counts a NaN as -inf"""
+    torch = _torch()
+    state = mtrend_init(data, 0, settings, given=mtrend_state(data, l0, m0, a, I_l, b, I_m))
+    S = MTREND_STATE
+    lb, ld = state[:, S["lik_b"]].clone(), state[:, S["lik_d"]].clone()
+    tot = lb + ld
+    return torch.where(torch.isnan(tot), torch.full_like(tot, float("-inf")), tot), lb, ld, state[:, S["prior"]].clone()
+
+
 def rjmc3_problem(data, state, swaps, seed, betas, swap_every=0, settings=RjbinSettings(), chain0=0):
     """The descriptor of a call on temperature ladders (_hip.Rjmc3Problem; it refers to the tensors of data, state and swaps
     and holds the host array of the betas: keep them alive while it is used).  betas: host floats [T], betas[0] = 1."""
